@@ -16,13 +16,31 @@ Every step inside the timed region does ALL of the above (nothing cached,
 no layers skipped).  Timed region: barrier + synchronize, K steps, barrier +
 synchronize; the MAX over ranks is reported.
 
-BASELINE.json's metric names the LSTM-attn decoder while the headline config
-(the reference default ``--num_chunks 1``) mean-pools the features, so an SCST
-run also times the 8-frame temporal-attention config of the same job (same K
-and W, after the headline run's buffers are freed) and reports it as the
-``att8`` field ({value, ms_per_step, ...}); ``--att8 0`` skips it.  After the
-timed steps the headline run also times the beam-5 evaluation decode of one
-batch (BASELINE config 5) on the weights it trained: the ``beam5`` field
+A plain run (``bench.py --gpus 1 --steps K --warmup W``) does only what the
+headline figure needs: set-up, W warm-up steps, K timed steps, the result
+line.  ``--dump-outputs DIR`` also writes what the last timed step returned
+to its caller (loss, reward, scores, sampled tokens) as ``DIR/<name>.npy``
+(float32 / float64, rank 0's shard); with the same arguments the inputs, and
+the RNG seeds, are identical from run to run, so two builds can be compared
+output for output.  The step itself is built to repeat bit for bit
+(counter-based RNG, fixed-order reductions, exact fixed-point sums where
+atomics decide the order), under two conditions nothing checks at run time:
+every per-token gate-gradient sum stays below 0.125 (embed_grad.hip; beyond
+that it rounds like any fp64 sum), and the hipBLASLt candidates picked by
+timing for the large GEMMs come out the same (``blaslt_x_choice`` shows
+them; two candidates within timing noise of the 4 % tie band, or another
+machine, can change them, and CSTCAP_BLASLT_ALGO pins one).
+
+``--full`` adds the other measurements of the same job, each a run of its
+own with the same K and W:  BASELINE.json's metric names the LSTM-attn
+decoder while the headline config (the reference default ``--num_chunks 1``)
+mean-pools the features, so a full SCST run also times the 8-frame
+temporal-attention config (after the headline run's buffers are freed) and
+reports it as the ``att8`` field ({value, ms_per_step, ...}); ``--att8 0``
+skips it.  Likewise the ``cst`` (CST recipe) and ``xe`` (cross-entropy
+stage) fields, ``--cst 0`` / ``--xe 0``.  After the timed steps the headline
+run of ``--full`` also times the beam-5 evaluation decode of one batch
+(BASELINE config 5) on the weights it trained: the ``beam5`` field
 ({videos_per_s (whole job), ms_per_batch, ...}); ``--beam5 0`` skips it.
 
 Modes:
@@ -86,6 +104,13 @@ def parse():
     p.add_argument('--num_layers', type=int, default=1)
     p.add_argument('--grad_wire', default='fp32', choices=['fp32', 'bf16'],
                    help='DP gradient reduction: fp32 all-reduce or bf16 wire / fp32 accumulation')
+    p.add_argument('--full', action='store_true',
+                   help='also run the measurements beyond the headline figure (--att8, '
+                        '--beam5, --cst, --xe: each on by default under --full); a plain run '
+                        'times the headline steps only')
+    p.add_argument('--dump-outputs', dest='dump_outputs', default='', metavar='DIR',
+                   help='after the timed steps, write what the last timed step returned (loss, '
+                        'reward, scores, sampled tokens; rank 0) as DIR/<name>.npy')
     p.add_argument('--att8', type=int, default=1,
                    help='scst with --num_chunks 1: also time the 8-frame temporal-attention '
                         'config in the same invocation and report it as the "att8" field')
@@ -146,11 +171,34 @@ def relaunch_if_needed(a):
     sys.exit(subprocess.call(cmd))
 
 
-def run_config(a, ctx, num_chunks, sync, sync_debug=0, mode=None):
+DUMP_BYTES = 64 << 20  # --dump-outputs: upper bound of all files together
+
+
+def dump_outputs(out, path):
+    """Write the tensors of a step's result as ``path/<name>.npy`` (float64
+    stays float64, everything else becomes float32: token ids are < 2^24).
+    An array over its share of DUMP_BYTES is cut to a fixed, seeded sample of
+    its elements (sorted flat indices)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    named = sorted((k, v) for k, v in out.items() if isinstance(v, torch.Tensor))
+    for k, v in named:
+        v = v.detach()
+        arr = v.to(torch.float64 if v.dtype == torch.float64 else torch.float32).cpu().numpy()
+        cap = DUMP_BYTES // len(named) // arr.itemsize
+        if arr.size > cap:
+            keep = np.sort(np.random.RandomState(0).choice(arr.size, cap, replace=False))
+            arr = arr.reshape(-1)[keep]
+        np.save(os.path.join(path, k + '.npy'), arr)
+
+
+def run_config(a, ctx, num_chunks, sync, sync_debug=0, mode=None, dump=''):
     """Build the dataset, model, engine and trainer for ``num_chunks`` frames
     per video, run ``a.warmup`` untimed and ``a.steps`` timed steps (barrier +
     synchronize on both sides, MAX over ranks) and free the GPU buffers.
-    ``mode`` overrides ``a.mode`` (the extra CST run of an SCST bench)."""
+    ``mode`` overrides ``a.mode`` (the extra CST run of an SCST bench);
+    ``dump``: directory for the last timed step's result (--dump-outputs)."""
     mode = mode or a.mode
     import gc
     import torch
@@ -212,7 +260,7 @@ def run_config(a, ctx, num_chunks, sync, sync_debug=0, mode=None):
             model.eval()
             with torch.no_grad():
                 seq, _ = model.sample(data['feats'], {'beam_size': a.beam_size})
-            return {'loss': seq.float().mean()}
+            return {'loss': seq.float().mean(), 'seq': seq}
         return trainer.train_step(data, 0)
 
     if a.stamps and dev.type == 'cuda':
@@ -252,6 +300,8 @@ def run_config(a, ctx, num_chunks, sync, sync_debug=0, mode=None):
     sync()
     dt = time.perf_counter() - t0
     dt = ctx.max_scalar(dt)
+    if dump and ctx.is_main:
+        dump_outputs(out, dump)
     stamp_mean = {}
     if a.stamps and dev.type == 'cuda':
         for _ in range(a.stamps):
@@ -269,7 +319,7 @@ def run_config(a, ctx, num_chunks, sync, sync_debug=0, mode=None):
             print('  %9.1f  %s' % (v, k), file=sys.stderr)
         sys.stderr.flush()
     beam = None
-    if (a.beam5 and mode == 'scst' and num_chunks == 1 and engine is not None
+    if (a.full and a.beam5 and mode == 'scst' and num_chunks == 1 and engine is not None
             and dev.type == 'cuda'):
         # BASELINE config 5: beam-5 evaluation decode of one batch (64 videos
         # per rank) with the weights the timed steps trained
@@ -346,9 +396,10 @@ def main():
     if a.impl == 'torch':
         os.environ['CSTCAP_ALLOW_TORCH_FALLBACK'] = '1'
     sync = torch.cuda.synchronize if ctx.device.type == 'cuda' else (lambda: None)
-    main_run = run_config(a, ctx, a.num_chunks, sync, sync_debug=a.sync_debug)
+    main_run = run_config(a, ctx, a.num_chunks, sync, sync_debug=a.sync_debug,
+                          dump=a.dump_outputs)
     att8 = None
-    if a.att8 and a.mode == 'scst' and a.num_chunks == 1:
+    if a.full and a.att8 and a.mode == 'scst' and a.num_chunks == 1:
         # the temporal-attention variant of the same job (8 frames per video),
         # same steps / warmup, measured after the headline run's buffers are freed
         r = run_config(a, ctx, 8, sync)
@@ -358,7 +409,7 @@ def main():
         if r['stamps']:
             att8['stamps_us'] = r['stamps']
     cst = None
-    if a.cst and a.mode == 'scst' and a.num_chunks == 1:
+    if a.full and a.cst and a.mode == 'scst' and a.num_chunks == 1:
         # the CST recipe of the same job (the reference's namesake), same steps
         # / warmup, after the previous runs' buffers are freed
         r = run_config(a, ctx, 1, sync, mode='cst')
@@ -367,7 +418,7 @@ def main():
                'scb_baseline': a.scb_baseline, 'scb_captions': 20, 'bcmr': r['bcmr'],
                'final_loss': r['loss'], 'skipped_steps': r['skipped']}
     xe = None
-    if a.xe and a.mode == 'scst' and a.num_chunks == 1:
+    if a.full and a.xe and a.mode == 'scst' and a.num_chunks == 1:
         # BASELINE config 2: the XE (teacher-forced cross-entropy) stage of the
         # same job on the same fused path (graph replay, X after the forward)
         r = run_config(a, ctx, 1, sync, mode='xe')

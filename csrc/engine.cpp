@@ -1237,14 +1237,15 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
   at::Tensor sort_ws = at::empty({2 * V + 1}, i32);
   at::Tensor stok = at::empty({NR}, i32), srow = at::empty({NR}, i32);
   at::Tensor S_tok = at::empty({V, H4}, wx.options());  // per-token gate-gradient sums
-  at::Tensor S32 = at::empty({V, H4}, f32);  // rows of long groups only (token_long_zero)
+  // rows of long groups only (token_long_zero); fp64: exact fixed-point sums
+  at::Tensor S64 = at::empty({V, H4}, f32.dtype(at::kDouble));
   // on the second side stream, off the critical path (needed after the loop)
   hipEvent_t ev_pre = aux.ev[6 + MAX_DHD_CHUNKS];
   (void)hipEventRecord(ev_pre, st);
   (void)hipStreamWaitEvent(side2.stream(), ev_pre, 0);
   launch_token_sort(toks.data_ptr<int64_t>(), (int)NR, (int)V, sort_ws.data_ptr<int>(),
                     stok.data_ptr<int>(), srow.data_ptr<int>(), side2.stream());
-  launch_token_long_zero(sort_ws.data_ptr<int>(), (int)V, (int)H4, S32.data_ptr<float>(),
+  launch_token_long_zero(sort_ws.data_ptr<int>(), (int)V, (int)H4, S64.data_ptr<double>(),
                          side2.stream());
   (void)hipEventRecord(ev_tok, side2.stream());
   if (x_wait != 0) (void)hipStreamWaitEvent(st, reinterpret_cast<hipEvent_t>(x_wait), 0);
@@ -1620,7 +1621,7 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
   launch_token_group_sum(reinterpret_cast<const uint16_t*>(dG_all.data_ptr()), (int)H4, KD,
                          stok.data_ptr<int>(), srow.data_ptr<int>(), (int)NR,
                          sort_ws.data_ptr<int>(), (int)V,
-                         reinterpret_cast<uint16_t*>(S_tok.data_ptr()), S32.data_ptr<float>(), st);
+                         reinterpret_cast<uint16_t*>(S_tok.data_ptr()), S64.data_ptr<double>(), st);
   stamp(STAMP_BWD_TOKSUM, st);
   late_dw(1);
   // d_emb = S W_ie (M = V, N = E, K = 4H): the measured hipBLASLt choice
@@ -2587,14 +2588,14 @@ at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V) {
   auto i32 = at::TensorOptions().dtype(at::kInt).device(toks.device());
   at::Tensor ws = at::empty({2 * V + 1}, i32), stok = at::empty({N}, i32), srow = at::empty({N}, i32);
   at::Tensor S = at::empty({V, C}, x.options());
-  at::Tensor S32 = at::empty({V, C}, x.options().dtype(at::kFloat));
+  at::Tensor S64 = at::empty({V, C}, x.options().dtype(at::kDouble));
   hipStream_t st = cur_stream();
   launch_token_sort(toks.data_ptr<int64_t>(), (int)N, (int)V, ws.data_ptr<int>(),
                     stok.data_ptr<int>(), srow.data_ptr<int>(), st);
-  launch_token_long_zero(ws.data_ptr<int>(), (int)V, (int)C, S32.data_ptr<float>(), st);
+  launch_token_long_zero(ws.data_ptr<int>(), (int)V, (int)C, S64.data_ptr<double>(), st);
   launch_token_group_sum(reinterpret_cast<const uint16_t*>(x.data_ptr()), (int)C, x.stride(0),
                          stok.data_ptr<int>(), srow.data_ptr<int>(), (int)N, ws.data_ptr<int>(),
-                         (int)V, reinterpret_cast<uint16_t*>(S.data_ptr()), S32.data_ptr<float>(),
+                         (int)V, reinterpret_cast<uint16_t*>(S.data_ptr()), S64.data_ptr<double>(),
                          st);
   return S;
 }

@@ -5,8 +5,8 @@
 // launches (a full-width radix sort of the int64 ids cost ~320 us per training
 // step), then per-token sums of the gate-gradient rows (token_group_sum).
 // The scatter takes slots with atomics, so the order of rows inside a token's
-// group varies between runs (summation order, as with PyTorch's own embedding
-// backward on GPUs).
+// group varies between runs; the sums below do not depend on it (exact
+// fixed-point accumulation), so the gradients are bit-identical run to run.
 #include "../common.h"
 
 namespace cst {
@@ -21,25 +21,34 @@ namespace cst {
 // start of the first group that begins in its chunk [GS_CHUNK b, GS_CHUNK (b +
 // 1)) to the END of the last such group, even past the chunk, so every group
 // of at most GS_LONG entries is summed by exactly one block, in a fixed order,
-// and stored once as bf16 (no atomics, no fp32 scratch).  Only
+// and stored once as bf16 (no atomics, no scratch).  Only
 // long groups (more than GS_LONG entries: the BOS token of step 0 has R of
-// them) are split at chunk boundaries; each chunk adds its part into the fp32
-// row S32[v] (zeroed by token_long_zero right after the sort, off the
+// them) are split at chunk boundaries; each chunk adds its part into the fp64
+// row S64[v] (zeroed by token_long_zero right after the sort, off the
 // critical path) and the finalize pass converts those rows and zero-fills the
-// tokens without entries.  (The former design zeroed a V x C fp32 scratch and
-// a flag array every step -- 86 MB -- and sent every chunk-spanning group
-// through atomics.)
+// tokens without entries.
+// Order independence: every addend is truncated to a multiple of 2^-GS_FIX
+// and accumulated as an integer-valued double, so partial sums are exact (and
+// associative: any row order, any split of a long group over chunks and any
+// order of their atomics give the same bits) while |sum| < 2^(53 - GS_FIX) =
+// 0.125; beyond that the sum rounds like any fp64 sum.  The truncation drops
+// less than 1.4e-17 per addend, far below the bf16 result's rounding.
+// (A former design zeroed a V x C fp32 scratch and a flag array every step
+// -- 86 MB -- and sent every chunk-spanning group through atomics.)
 // Thread t owns the 8-column chunks t + 256 j of every row (one 16-byte load
 // per thread and row, GS_PF rows in flight); the block's entry indices are
 // staged in LDS.
 constexpr int GS_CHUNK = 64, GS_LONG = 192, GS_PF = 8;
+constexpr double GS_SCALE = 0x1p56, GS_UNSCALE = 0x1p-56;  // 2^GS_FIX, GS_FIX = 56
+__device__ __forceinline__ double gs_fix(float x) { return __builtin_trunc((double)x * GS_SCALE); }
+__device__ __forceinline__ float gs_unfix(double a) { return (float)(a * GS_UNSCALE); }
 constexpr int GS_SPAN = GS_CHUNK + GS_LONG;  // entries one block can own
 
 template <int MAXJ>
 __global__ __launch_bounds__(256) void token_group_sum_kernel(
     const uint16_t* __restrict__ x, int C, int64_t ld, const int* __restrict__ stok,
     const int* __restrict__ srow, const int* __restrict__ ws, int V, uint16_t* __restrict__ S,
-    float* __restrict__ S32) {
+    double* __restrict__ S64) {
   __shared__ int s_tok[GS_SPAN];
   __shared__ int s_row[GS_SPAN];
   const int* count = ws;
@@ -66,11 +75,11 @@ __global__ __launch_bounds__(256) void token_group_sum_kernel(
   }
   __syncthreads();
   const int nch = C >> 3;
-  float acc[MAXJ][8];
+  double acc[MAXJ][8];
 #pragma unroll
   for (int j = 0; j < MAXJ; ++j)
 #pragma unroll
-    for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
+    for (int k = 0; k < 8; ++k) acc[j][k] = 0.0;
   auto flush = [&](int tf) {
     const int v = tf & 0x7fffffff;
     if (tf >= 0) {  // whole group in this block: final value
@@ -79,10 +88,10 @@ __global__ __launch_bounds__(256) void token_group_sum_kernel(
         const int c = tid + 256 * j;
         if (c < nch) {
           uint4 o;
-          o.x = (uint32_t)f2bf(acc[j][0]) | ((uint32_t)f2bf(acc[j][1]) << 16);
-          o.y = (uint32_t)f2bf(acc[j][2]) | ((uint32_t)f2bf(acc[j][3]) << 16);
-          o.z = (uint32_t)f2bf(acc[j][4]) | ((uint32_t)f2bf(acc[j][5]) << 16);
-          o.w = (uint32_t)f2bf(acc[j][6]) | ((uint32_t)f2bf(acc[j][7]) << 16);
+          o.x = (uint32_t)f2bf(gs_unfix(acc[j][0])) | ((uint32_t)f2bf(gs_unfix(acc[j][1])) << 16);
+          o.y = (uint32_t)f2bf(gs_unfix(acc[j][2])) | ((uint32_t)f2bf(gs_unfix(acc[j][3])) << 16);
+          o.z = (uint32_t)f2bf(gs_unfix(acc[j][4])) | ((uint32_t)f2bf(gs_unfix(acc[j][5])) << 16);
+          o.w = (uint32_t)f2bf(gs_unfix(acc[j][6])) | ((uint32_t)f2bf(gs_unfix(acc[j][7])) << 16);
           *reinterpret_cast<uint4*>(S + (int64_t)v * C + 8 * c) = o;
         }
       }
@@ -97,13 +106,13 @@ __global__ __launch_bounds__(256) void token_group_sum_kernel(
         if (c < nch)
 #pragma unroll
           for (int k = 0; k < 8; ++k)
-            if (acc[j][k] != 0.f) atomicAdd(S32 + (int64_t)v * C + 8 * c + k, acc[j][k]);
+            if (acc[j][k] != 0.0) atomicAdd(S64 + (int64_t)v * C + 8 * c + k, acc[j][k]);
       }
     }
 #pragma unroll
     for (int j = 0; j < MAXJ; ++j)
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc[j][k] = 0.f;
+      for (int k = 0; k < 8; ++k) acc[j][k] = 0.0;
   };
   // Double-buffered batches of GS_PF rows: the next batch's loads are issued
   // before the current batch is summed, every load unconditional (row index
@@ -143,8 +152,8 @@ __global__ __launch_bounds__(256) void token_group_sum_kernel(
           const uint32_t w[4] = {cb[p][j].x, cb[p][j].y, cb[p][j].z, cb[p][j].w};
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
-            acc[j][2 * k] += live ? bf2f(w[k] & 0xffff) : 0.f;
-            acc[j][2 * k + 1] += live ? bf2f(w[k] >> 16) : 0.f;
+            acc[j][2 * k] += live ? gs_fix(bf2f(w[k] & 0xffff)) : 0.0;
+            acc[j][2 * k + 1] += live ? gs_fix(bf2f(w[k] >> 16)) : 0.0;
           }
         }
       }
@@ -159,20 +168,20 @@ __global__ __launch_bounds__(256) void token_group_sum_kernel(
   flush(cur);
 }
 
-// one wavefront per token: zero the fp32 rows of long groups (before the sums)
+// one wavefront per token: zero the fp64 rows of long groups (before the sums)
 __global__ __launch_bounds__(256) void token_long_zero_kernel(int V, int C,
                                                               const int* __restrict__ count,
-                                                              float* __restrict__ S32) {
+                                                              double* __restrict__ S64) {
   const int v = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (v >= V || count[v] <= GS_LONG) return;
-  for (int c = lane; c < (C >> 2); c += 64)
-    reinterpret_cast<float4*>(S32 + (int64_t)v * C)[c] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int c = lane; c < (C >> 1); c += 64)
+    reinterpret_cast<double2*>(S64 + (int64_t)v * C)[c] = make_double2(0.0, 0.0);
 }
 
 // one wavefront per token: zero rows of tokens without entries, convert the
-// long groups' rows from the fp32 scratch
+// long groups' rows from the fp64 scratch
 __global__ __launch_bounds__(256) void token_group_finalize_kernel(
-    int V, int C, const int* __restrict__ count, const float* __restrict__ S32,
+    int V, int C, const int* __restrict__ count, const double* __restrict__ S64,
     uint16_t* __restrict__ S) {
   const int v = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (v >= V) return;
@@ -182,26 +191,26 @@ __global__ __launch_bounds__(256) void token_group_finalize_kernel(
   for (int c = lane; c < (C >> 3); c += 64) {
     uint4 o = make_uint4(0, 0, 0, 0);
     if (!empty) {
-      const float4 a = reinterpret_cast<const float4*>(S32 + (int64_t)v * C + 8 * c)[0];
-      const float4 b = reinterpret_cast<const float4*>(S32 + (int64_t)v * C + 8 * c)[1];
-      o.x = (uint32_t)f2bf(a.x) | ((uint32_t)f2bf(a.y) << 16);
-      o.y = (uint32_t)f2bf(a.z) | ((uint32_t)f2bf(a.w) << 16);
-      o.z = (uint32_t)f2bf(b.x) | ((uint32_t)f2bf(b.y) << 16);
-      o.w = (uint32_t)f2bf(b.z) | ((uint32_t)f2bf(b.w) << 16);
+      const double2* q = reinterpret_cast<const double2*>(S64 + (int64_t)v * C + 8 * c);
+      const double2 a = q[0], b = q[1], d = q[2], e = q[3];
+      o.x = (uint32_t)f2bf(gs_unfix(a.x)) | ((uint32_t)f2bf(gs_unfix(a.y)) << 16);
+      o.y = (uint32_t)f2bf(gs_unfix(b.x)) | ((uint32_t)f2bf(gs_unfix(b.y)) << 16);
+      o.z = (uint32_t)f2bf(gs_unfix(d.x)) | ((uint32_t)f2bf(gs_unfix(d.y)) << 16);
+      o.w = (uint32_t)f2bf(gs_unfix(e.x)) | ((uint32_t)f2bf(gs_unfix(e.y)) << 16);
     }
     *reinterpret_cast<uint4*>(S + (int64_t)v * C + 8 * c) = o;
   }
 }
 
-void launch_token_long_zero(const int* ws, int V, int C, float* S32, hipStream_t stream) {
-  if (C % 4 != 0) throw std::runtime_error("token_long_zero: C must be a multiple of 4");
+void launch_token_long_zero(const int* ws, int V, int C, double* S64, hipStream_t stream) {
+  if (C % 2 != 0) throw std::runtime_error("token_long_zero: C must be even");
   hipLaunchKernelGGL(token_long_zero_kernel, dim3((V + 3) / 4), dim3(256), 0, stream, V, C, ws,
-                     S32);
+                     S64);
   post_launch("token_long_zero_kernel", stream);
 }
 
 void launch_token_group_sum(const uint16_t* x, int C, int64_t ld, const int* stok,
-                            const int* srow, int N, const int* ws, int V, uint16_t* S, float* S32,
+                            const int* srow, int N, const int* ws, int V, uint16_t* S, double* S64,
                             hipStream_t stream) {
   if (C % 8 != 0 || C > 256 * 8 * 2 || ld % 8 != 0)
     throw std::runtime_error("token_group_sum: C and ld multiples of 8, C <= 4096");
@@ -210,13 +219,13 @@ void launch_token_group_sum(const uint16_t* x, int C, int64_t ld, const int* sto
   const dim3 grid((N + GS_CHUNK - 1) / GS_CHUNK);
   if (C <= 256 * 8)
     hipLaunchKernelGGL(token_group_sum_kernel<1>, grid, dim3(256), 0, stream, x, C, ld, stok, srow,
-                       ws, V, S, S32);
+                       ws, V, S, S64);
   else
     hipLaunchKernelGGL(token_group_sum_kernel<2>, grid, dim3(256), 0, stream, x, C, ld, stok, srow,
-                       ws, V, S, S32);
+                       ws, V, S, S64);
   post_launch("token_group_sum_kernel", stream);
   hipLaunchKernelGGL(token_group_finalize_kernel, dim3((V + 3) / 4), dim3(256), 0, stream, V, C,
-                     ws, S32, S);
+                     ws, S64, S);
   post_launch("token_group_finalize_kernel", stream);
 }
 

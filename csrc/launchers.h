@@ -432,11 +432,11 @@ void launch_xe_loss_bwd(const float* cnt, const float* out, const float* dloss, 
 
 // embed_grad.hip
 // per-token sums S[v] (bf16, V x C) of the bf16 rows x[srow[i]] (row stride ld)
-// over a token sort (ws = its workspace: counts, group ends); S32 (V x C fp32
+// over a token sort (ws = its workspace: counts, group ends); S64 (V x C fp64
 // scratch) must have been prepared by launch_token_long_zero after the sort
-void launch_token_long_zero(const int* ws, int V, int C, float* S32, hipStream_t stream);
+void launch_token_long_zero(const int* ws, int V, int C, double* S64, hipStream_t stream);
 void launch_token_group_sum(const uint16_t* x, int C, int64_t ld, const int* stok,
-                            const int* srow, int N, const int* ws, int V, uint16_t* S, float* S32,
+                            const int* srow, int N, const int* ws, int V, uint16_t* S, double* S64,
                             hipStream_t stream);
 // Weight-gradient GEMM C = A^T B of K-major bf16 operands (kernels/wgrad.hip):
 // A (K x >= M, row stride lda), B (K x >= N, ldb); rows [0, M0) of C go to C0

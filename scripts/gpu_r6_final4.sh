@@ -1,10 +1,11 @@
 #!/bin/bash
 # round 6 session 2, last call: the host-UBSan engine test + smoke on the final
 # .so files, a PMC pass set of the replayed att8 step, and the beam-5 step table
+export OUT=${OUT:-bench_out}  # output directory (inherited by the scripts called from here)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-D=gpurun_out/final_s2c
+D=$OUT/final_s2c
 mkdir -p $D
 timeout -k 10 600 python -u -m pytest -x -v --timeout 300 --timeout-method thread -p no:cacheprovider \
   tests/test_gpu_debug.py tests/test_gpu_dist.py > $D/pytest_debug_dist.log 2>&1 || { tail -40 $D/pytest_debug_dist.log; exit 1; }

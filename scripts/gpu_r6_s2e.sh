@@ -1,24 +1,25 @@
 #!/bin/bash
 # round 6 session 2: XE all-rows forward (one vocabulary launch over T x R rows)
+export OUT=${OUT:-bench_out}  # output directory (inherited by the scripts called from here)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out/s2e
+mkdir -p $OUT/s2e
 timeout -k 10 700 python -u -m pytest -x -v --timeout 300 --timeout-method thread -p no:cacheprovider \
   tests/test_gpu_headline.py tests/test_gpu_kernels.py tests/test_gpu_cells.py tests/test_gpu_graph.py \
   tests/test_gpu_bwd_loop.py tests/test_gpu_decode_step.py \
-  > gpurun_out/s2e/pytest.log 2>&1 || { tail -40 gpurun_out/s2e/pytest.log; exit 1; }
-tail -1 gpurun_out/s2e/pytest.log
+  > $OUT/s2e/pytest.log 2>&1 || { tail -40 $OUT/s2e/pytest.log; exit 1; }
+tail -1 $OUT/s2e/pytest.log
 for i in 1 2; do
   for m in 1 0; do
-    CSTCAP_XE_ROWS=$m timeout -k 10 300 python bench.py --att8 0 --beam5 0 --cst 0 > gpurun_out/s2e/xe${m}_$i.log 2>&1 || { tail -20 gpurun_out/s2e/xe${m}_$i.log; exit 1; }
-    grep '^{' gpurun_out/s2e/xe${m}_$i.log > gpurun_out/s2e/xe${m}_$i.json
-    python -c "import json; d=json.load(open('gpurun_out/s2e/xe${m}_$i.json')); print('xe_rows=$m scst', d['ms_per_step'], 'xe', d['xe']['ms_per_step'], 'xe_loss', d['xe']['final_loss'], 'err', d['device_errors'])"
+    CSTCAP_XE_ROWS=$m timeout -k 10 300 python bench.py --full --att8 0 --beam5 0 --cst 0 > $OUT/s2e/xe${m}_$i.log 2>&1 || { tail -20 $OUT/s2e/xe${m}_$i.log; exit 1; }
+    grep '^{' $OUT/s2e/xe${m}_$i.log > $OUT/s2e/xe${m}_$i.json
+    python -c "import json; d=json.load(open('$OUT/s2e/xe${m}_$i.json')); print('xe_rows=$m scst', d['ms_per_step'], 'xe', d['xe']['ms_per_step'], 'xe_loss', d['xe']['final_loss'], 'err', d['device_errors'])"
   done
 done
-rm -rf gpurun_out/s2e/prof
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/s2e/prof -o xe -- \
-    python bench.py --mode xe --steps 10 --warmup 5 --att8 0 --beam5 0 --cst 0 > gpurun_out/s2e/prof.log 2>&1 || exit $?
-python scripts/prof_steps.py gpurun_out/s2e/prof/xe_kernel_trace.csv 10 30 adam_update_kernel 'e' > gpurun_out/s2e/steps_xe.txt || exit $?
-rm -f gpurun_out/s2e/prof/xe_kernel_trace.csv
-head -24 gpurun_out/s2e/steps_xe.txt | cut -c1-110
+rm -rf $OUT/s2e/prof
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/s2e/prof -o xe -- \
+    python bench.py --mode xe --steps 10 --warmup 5 --att8 0 --beam5 0 --cst 0 > $OUT/s2e/prof.log 2>&1 || exit $?
+python scripts/prof_steps.py $OUT/s2e/prof/xe_kernel_trace.csv 10 30 adam_update_kernel 'e' > $OUT/s2e/steps_xe.txt || exit $?
+rm -f $OUT/s2e/prof/xe_kernel_trace.csv
+head -24 $OUT/s2e/steps_xe.txt | cut -c1-110

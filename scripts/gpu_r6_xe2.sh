@@ -1,11 +1,12 @@
 #!/bin/bash
 # round 6: XE step kernel table + launch sequence
+export OUT=${OUT:-bench_out}  # output directory (inherited by the scripts called from here)
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 export TMPDIR=/tmp
-mkdir -p gpurun_out
-rm -rf gpurun_out/prof_xe
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_xe -o xe -- python bench.py --mode xe --steps 10 --warmup 5 --att8 0 --beam5 0 --cst 0 --xe 0 > gpurun_out/prof_xe.log 2>&1 || exit $?
-grep '^{' gpurun_out/prof_xe.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('xe', d['ms_per_step'], 'dev_err', d.get('device_errors'))"
-python scripts/prof_steps.py gpurun_out/prof_xe/xe_kernel_trace.csv 10 24 adam_update_kernel 'e' > gpurun_out/steps_xe.txt && head -n 26 gpurun_out/steps_xe.txt
-rm -f gpurun_out/prof_xe/xe_kernel_trace.csv
+mkdir -p $OUT
+rm -rf $OUT/prof_xe
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_xe -o xe -- python bench.py --mode xe --steps 10 --warmup 5 --att8 0 --beam5 0 --cst 0 --xe 0 > $OUT/prof_xe.log 2>&1 || exit $?
+grep '^{' $OUT/prof_xe.log | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('xe', d['ms_per_step'], 'dev_err', d.get('device_errors'))"
+python scripts/prof_steps.py $OUT/prof_xe/xe_kernel_trace.csv 10 24 adam_update_kernel 'e' > $OUT/steps_xe.txt && head -n 26 $OUT/steps_xe.txt
+rm -f $OUT/prof_xe/xe_kernel_trace.csv

@@ -9,7 +9,7 @@ import torch
 
 import bench  # noqa: E402
 
-sys.argv = ['bench.py', '--steps', '3', '--warmup', '3']
+sys.argv = ['bench.py', '--steps', '3', '--warmup', '3', '--full']
 state = {}
 _orig = torch.cuda.CUDAGraph.replay
 

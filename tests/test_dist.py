@@ -36,6 +36,7 @@ def _run(world, out, wire='fp32', update='allreduce', mode='xe'):
     env['CSTCAP_TEST_DPUPDATE'] = update
     env['PYTHONPATH'] = ROOT + os.pathsep + env.get('PYTHONPATH', '')
     env['CUDA_VISIBLE_DEVICES'] = ''  # CPU ranks (gloo)
+    env['HIP_VISIBLE_DEVICES'] = ''  # (set on ROCm hosts, it outranks the CUDA_ name)
     env['OMP_NUM_THREADS'] = '1'
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1',
            '--nproc-per-node', str(world), '--master-addr', '127.0.0.1',

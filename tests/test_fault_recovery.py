@@ -32,7 +32,7 @@ def test_killed_rank_resumes_from_last_sidecar(tmp_path):
     marker = str(tmp_path / 'fault_fired')
     env = dict(os.environ)
     env.update(PYTHONPATH=ROOT + os.pathsep + env.get('PYTHONPATH', ''), CUDA_VISIBLE_DEVICES='',
-               OMP_NUM_THREADS='1', CSTCAP_FAULT_INJECT='1:7:' + marker)
+               HIP_VISIBLE_DEVICES='', OMP_NUM_THREADS='1', CSTCAP_FAULT_INJECT='1:7:' + marker)
     # 24 videos / (4 per rank x 2 ranks) = 3 iterations per epoch; the sidecar
     # is written at iter 6 (epoch 2), rank 1 dies at iter 7.
     args = ['--synthetic', 'msvd', '--synthetic_videos', '24', '--synthetic_vocab', '40',
@@ -77,7 +77,7 @@ def test_resume_after_validated_epoch_matches_uninterrupted(tmp_path):
     def launch(mf, fault=None):
         env = dict(os.environ)
         env.update(PYTHONPATH=ROOT + os.pathsep + env.get('PYTHONPATH', ''),
-                   CUDA_VISIBLE_DEVICES='', OMP_NUM_THREADS='1')
+                   CUDA_VISIBLE_DEVICES='', HIP_VISIBLE_DEVICES='', OMP_NUM_THREADS='1')
         env.pop('CSTCAP_FAULT_INJECT', None)
         if fault:
             env['CSTCAP_FAULT_INJECT'] = fault

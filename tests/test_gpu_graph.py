@@ -214,7 +214,7 @@ def test_token_counting_sort():
 def test_token_group_sums(C):
     """Per-token row sums (embedding / input-weight gradient operand): short
     groups summed by their owning block, long groups (the BOS / EOS buckets,
-    groups of 200-300 entries around the 192-entry split) through the fp32
+    groups of 200-300 entries around the 192-entry split) through the fp64
     scratch, and tokens without rows zero-filled -- against an fp32
     index_add."""
     from cst_captioning_amd import _ext
@@ -232,6 +232,29 @@ def test_token_group_sums(C):
     assert S.dtype == torch.bfloat16 and S.shape == (V, C)
     assert torch.all(S[V - 50:] == 0)   # tokens without rows
     err = (S.float() - ref).norm() / ref.norm()
+    assert err < 4e-3, err
+
+
+def test_token_group_sums_do_not_depend_on_the_row_order():
+    """The sums are exact fixed-point sums (embed_grad.hip), so the order of
+    the rows inside a group -- which the sort's atomics leave open, and which
+    decides the split of a long group over chunks -- must not change one bit:
+    the same rows in another order give the identical result.  Gradient-sized
+    values (|sum| < 0.125, the exact range)."""
+    from cst_captioning_amd import _ext
+    V, N, C = 10509, 28 * 1280, 2048
+    g = torch.Generator(device='cpu').manual_seed(5)
+    toks = torch.randint(1, V, (N,), generator=g)
+    toks[:1280] = 0                     # a long group: split over 20 chunks
+    toks[5000:5250] = 7
+    x = (torch.randn(N, C, generator=g) * 1e-4).to(torch.bfloat16)
+    perm = torch.randperm(N, generator=g)
+    S0 = _ext.ops().token_group_sum(x.to(DEV), toks.to(DEV), V)
+    S1 = _ext.ops().token_group_sum(x[perm].to(DEV), toks[perm].to(DEV), V)
+    assert float(S0.float().abs().max()) > 0
+    assert torch.equal(S0, S1)
+    ref = torch.zeros(V, C, dtype=torch.float64).index_add_(0, toks, x.double())
+    err = (S0.cpu().double() - ref).norm() / ref.norm()
     assert err < 4e-3, err
 
 

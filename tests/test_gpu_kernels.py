@@ -686,3 +686,42 @@ def test_tuned_blaslt_gemm_matches_torch(batched):
         ops.gemm_bf16_tuned_batched(out, a, True, b, False)
         ref = torch.bmm(a.float().transpose(1, 2), b.float())
         torch.testing.assert_close(out, ref, rtol=2e-5, atol=2e-4)
+
+
+def test_tuned_blaslt_gemm_timed_choice_and_tiny_shapes():
+    """The tuner's two paths (csrc/host/blaslt_tuned.cpp).  A GEMM of at least
+    4 GFLOP (520 x 4096, K = 1024: 4.36 GFLOP) is timed: its candidates'
+    timings are recorded, the choice is the FIRST candidate within 4 % of the
+    fastest (near-ties must not alternate between runs), and the result
+    matches the fp32 product (atol: the K = 256 bound of the test above times
+    4, rounding error growing at most linearly in K).  A GEMM below the
+    threshold takes the heuristic's first candidate without any timing."""
+    from cst_captioning_amd import _ext
+    ops = _ext.ops()
+    torch.manual_seed(1)
+
+    def choice(M, N, K):
+        c = [r for r in ops.gemm_tuned_choices() if (r[0], r[1], r[2]) == (N, M, K)]
+        assert len(c) == 1, c
+        return int(c[0][3]), c[0][4]
+
+    K, M, N = 1024, 520, 4096
+    a = torch.randn(K, M, device=DEV).to(torch.bfloat16)
+    b = torch.randn(K, N, device=DEV).to(torch.bfloat16)
+    out = torch.empty(M, N, device=DEV)
+    ops.gemm_bf16_tuned(out, a, True, b, False)
+    torch.testing.assert_close(out, a.float().t() @ b.float(), rtol=2e-5, atol=8e-4)
+    us = ops.gemm_tuned_timings(out, a, True, b, False)
+    assert len(us) >= 1 and min(us) > 0
+    _, chosen_us = choice(M, N, K)
+    first_in_band = next(t for t in us if t <= min(us) * 1.04)
+    assert abs(chosen_us - first_in_band) < 1e-9, (chosen_us, us)
+
+    K, M, N = 72, 136, 264  # 5 MFLOP
+    a = torch.randn(K, M, device=DEV).to(torch.bfloat16)
+    b = torch.randn(K, N, device=DEV).to(torch.bfloat16)
+    out = torch.empty(M, N, device=DEV)
+    ops.gemm_bf16_tuned(out, a, True, b, False)
+    torch.testing.assert_close(out, a.float().t() @ b.float(), rtol=2e-5, atol=2e-4)
+    assert ops.gemm_tuned_timings(out, a, True, b, False) == []
+    assert choice(M, N, K) == (0, -1.0)
