@@ -15,7 +15,7 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
                                         bool use_unfinished, std::vector<at::Tensor> att,
                                         int64_t cell, std::vector<at::Tensor> state0,
                                         std::vector<at::Tensor> up, bool store_exp,
-                                        bool xe_rows);
+                                        bool xe_rows, c10::optional<at::Tensor> lab_idx);
 void set_grad_events(bool on);
 void grad_event_wait(int64_t k, int64_t stream);
 void grad_event_record(int64_t k, int64_t stream);
@@ -48,7 +48,8 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
                                          at::Tensor fix_total, int64_t vgate_div,
                                          at::Tensor xw, std::vector<at::Tensor> vg_bwd,
                                          int64_t vg_nf, double vg_p, int64_t x_wait,
-                                         bool exp_zero_off);
+                                         bool exp_zero_off, std::vector<at::Tensor> dw_slots,
+                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C);
 std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor whh,
                                     at::Tensor wlog, at::Tensor blog, at::Tensor vgate,
                                     int64_t K, int64_t T, int64_t bos_index,
@@ -69,11 +70,17 @@ at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, in
 at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
                               at::Tensor dloss);
 at::Tensor featpool_forward(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
-                            std::vector<at::Tensor> bs, double drop_p, at::Tensor rng);
+                            std::vector<at::Tensor> bs, double drop_p, at::Tensor rng,
+                            c10::optional<at::Tensor> idx, int64_t C);
+std::vector<at::Tensor> featpool_forward16(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
+                                           std::vector<at::Tensor> bs, double drop_p,
+                                           at::Tensor rng, c10::optional<at::Tensor> idx,
+                                           int64_t C);
 std::vector<at::Tensor> featpool_backward(at::Tensor dout, at::Tensor out,
                                           std::vector<at::Tensor> xs,
                                           std::vector<at::Tensor> ws, double drop_p,
-                                          std::vector<at::Tensor> outs);
+                                          std::vector<at::Tensor> outs,
+                                          c10::optional<at::Tensor> idx, int64_t C);
 std::vector<at::Tensor> att_mfma_fwd(at::Tensor h, at::Tensor wq, at::Tensor P, at::Tensor wa,
                                      at::Tensor ba, at::Tensor gv,
                                      int64_t whole);
@@ -105,6 +112,8 @@ int64_t wall_clock_khz();
 void vocab_x(at::Tensor logits16, at::Tensor wlog, at::Tensor out);
 at::Tensor att_mfma_phases(at::Tensor gv, at::Tensor P, at::Tensor wa, at::Tensor ba, int64_t R);
 at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K);
+void wgrad_tn_rows(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K, at::Tensor out,
+                   at::Tensor rmap);
 std::vector<at::Tensor> wgrad_tn_colsum(at::Tensor A, at::Tensor B, at::Tensor al, int64_t M,
                                         int64_t N, int64_t K);
 
@@ -169,7 +178,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out_emb"), py::arg("ds_bias"), py::arg("cell"), py::arg("state0"), py::arg("up"),
         py::arg("blog"), py::arg("fix_total"), py::arg("vgate_div"), py::arg("xw"),
         py::arg("vg_bwd"), py::arg("vg_nf"), py::arg("vg_p"), py::arg("x_wait") = 0,
-        py::arg("exp_zero_off") = false);
+        py::arg("exp_zero_off") = false, py::arg("dw_slots") = std::vector<at::Tensor>(),
+        py::arg("vg_idx") = py::none(), py::arg("vg_C") = 1);
   m.def("cider_build_tables", &cst::cider_build_tables);
   m.def("cider_score", &cst::cider_score);
   m.def("cider_score_cpu", &cst::cider_score_cpu);
@@ -209,13 +219,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("att_mfma_fwd", &cst::att_mfma_fwd, py::arg("h"), py::arg("wq"), py::arg("P"),
         py::arg("wa"), py::arg("ba"), py::arg("gv"), py::arg("whole") = -1);
   m.def("beam_search", &cst::beam_search);
-  m.def("featpool_forward", &cst::featpool_forward);
+  // idx / C: optional int64 row index into resident feature tables (C frames per row)
+  m.def("featpool_forward", &cst::featpool_forward, py::arg("xs"), py::arg("ws"), py::arg("bs"),
+        py::arg("drop_p"), py::arg("rng"), py::arg("idx") = py::none(), py::arg("C") = 1);
+  m.def("featpool_forward16", &cst::featpool_forward16, py::arg("xs"), py::arg("ws"),
+        py::arg("bs"), py::arg("drop_p"), py::arg("rng"), py::arg("idx") = py::none(),
+        py::arg("C") = 1);
   m.def("scst_loss_forward", &cst::scst_loss_forward);
   m.def("cst_loss_forward", &cst::cst_loss_forward);
   m.def("scst_loss_backward", &cst::scst_loss_backward);
   m.def("xe_loss_forward", &cst::xe_loss_forward);
   m.def("xe_loss_backward", &cst::xe_loss_backward);
-  m.def("featpool_backward", &cst::featpool_backward);
+  m.def("featpool_backward", &cst::featpool_backward, py::arg("dout"), py::arg("out"),
+        py::arg("xs"), py::arg("ws"), py::arg("drop_p"), py::arg("outs"),
+        py::arg("idx") = py::none(), py::arg("C") = 1);
   m.def("set_stamp_base", &cst::set_stamp_base);
   m.def("stamp_buffer", &cst::stamp_buffer);
   m.def("stamp_now", &cst::stamp_now);
@@ -226,4 +243,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("att_mfma_phases", &cst::att_mfma_phases);
   m.def("wgrad_tn", &cst::wgrad_tn);
   m.def("wgrad_tn_colsum", &cst::wgrad_tn_colsum);
+  m.def("wgrad_tn_rows", &cst::wgrad_tn_rows);
 }

@@ -308,7 +308,7 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
                                         bool use_unfinished, std::vector<at::Tensor> att,
                                         int64_t cell, std::vector<at::Tensor> state0,
                                         std::vector<at::Tensor> up, bool store_exp,
-                                        bool xe_rows) {
+                                        bool xe_rows, c10::optional<at::Tensor> lab_idx) {
   check_cuda(wx, "wx");
   TORCH_CHECK(cell >= 0 && cell <= 2, "cell: 0 lstm, 1 gru, 2 rnn (tanh)");  // CellType (common.h)
   check_cuda(emb, "emb");
@@ -361,10 +361,24 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
   }
   TORCH_CHECK(T >= 2 && (int64_t)modes.size() >= T - 1, "modes must cover T-1 steps");
   const bool have_labels = labels.defined() && labels.numel() > 0;
+  const bool have_idx = have_labels && lab_idx.has_value() && lab_idx->defined() &&
+                        lab_idx->numel() > 0;
   int64_t L = 0;
   if (have_labels) {
     check_cuda(labels, "labels");
-    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.size(0) == R, "labels (R, L) int64");
+    // lab_idx: labels is the resident (captions, L) label table and row r of
+    // this call is its row lab_idx[r] -- every reader below takes the index
+    // (TokRows), no gathered copy is made
+    TORCH_CHECK(labels.scalar_type() == at::kLong && labels.dim() == 2 && labels.is_contiguous() &&
+                    (have_idx || labels.size(0) == R), "labels (R, L) int64");
+    if (have_idx) {
+      check_cuda(*lab_idx, "lab_idx");
+      TORCH_CHECK(lab_idx->scalar_type() == at::kLong && lab_idx->is_contiguous() &&
+                      lab_idx->numel() == R && labels.size(0) >= 1,
+                  "lab_idx: (R) int64 rows of the label table");
+      // (teacher forcing keeps the gathered copy: its loss reads it anyway)
+      TORCH_CHECK(!xe_rows && !want_xe, "want_xe / xe_rows read a gathered (R, L) label copy");
+    }
     L = labels.size(1);
     TORCH_CHECK(L >= T + (want_xe ? 1 : 0), "labels too short for T steps");
   } else {
@@ -385,12 +399,24 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
   at::Tensor lse = at::empty({n_steps, R}, f32);
   at::Tensor part =
       at::empty({(int64_t)vocab_part_slots((int)V) * R * vocab_partial_bytes() / 4}, f32);
-  // the end-of-sequence flags of every step (zero-filled)
+  // the end-of-sequence flags of every step and the row masks: no fill
+  // launches -- the decode's first launch (lstm_step_fwd, step 0) zeroes the
+  // flag words and sets the masks before any combine reads them (StepInit)
   const int64_t n_cnt = (T + 1) * combine_count_ints_per_step();
-  at::Tensor counts = at::zeros({n_cnt}, at::TensorOptions().dtype(at::kInt).device(dev));
+  at::Tensor counts = at::empty({n_cnt}, at::TensorOptions().dtype(at::kInt).device(dev));
   at::Tensor unfinished =
-      use_unfinished ? at::ones({R}, at::TensorOptions().dtype(at::kByte).device(dev))
+      use_unfinished ? at::empty({R}, at::TensorOptions().dtype(at::kByte).device(dev))
                      : at::Tensor();
+  StepInit sinit{};
+  if (use_counts) {
+    sinit.flags = counts.data_ptr<int>();
+    sinit.n_flags = (int)(T + 1) * combine_count_slots();
+    sinit.stride = combine_count_ints_per_step() / combine_count_slots();
+  }
+  if (use_unfinished) {
+    sinit.ones = unfinished.data_ptr<uint8_t>();
+    sinit.n_ones = (int)R;
+  }
   // saved rows padded to 128 bytes (whole cache lines per row)
   const int64_t ldl = (V + 63) / 64 * 64;
   // Stacked layers (num_layers > 1): layer 0 is the fused pipeline below;
@@ -462,6 +488,9 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
   const uint16_t* W = reinterpret_cast<const uint16_t*>(wlog.data_ptr());
   const uint16_t* WHH = reinterpret_cast<const uint16_t*>(whh.data_ptr());
   const int64_t* LAB = have_labels ? labels.data_ptr<int64_t>() : nullptr;
+  // the label rows as every kernel below reads them (by index where given)
+  const TokRows LABR(LAB, have_idx ? lab_idx->data_ptr<int64_t>() : nullptr,
+                     have_idx ? labels.size(0) : 0);
 
   // initial state (model_type 'standard': the state after the video step;
   // otherwise zero): state0 = {h0 bf16 (R, H), c0 fp32 (R, H)}
@@ -588,6 +617,8 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
     at::Tensor tgt_all = labels.narrow(1, 1, n_steps).t().contiguous();  // (n_steps, R)
     at::Tensor gx = at::empty({n_steps, R}, f32);
     stamp(STAMP_FWD_BEGIN, st);
+    // (no StepInit: this path passes null counts to its one combine and never
+    // returns the buffer, so the flag words stay unwritten and unread)
     launch_lstm_step_fwd(LAB, L, PTAB, nullptr, nullptr, VG, VDIV, (int)R, (int)H, WHH,
                          h_buf(0, 0), c_buf(0, 0), hd_buf(0, 0), (int)H, (float)drop_p, RNG,
                          key(0, 0), gates_buf(0, 0), st, nullptr, (int)cell);
@@ -622,12 +653,12 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
   stamp(STAMP_FWD_BEGIN, st);
   if (has_att) run_att(0);
   // (zero initial state: null h / c, the kernel skips the recurrent GEMM)
-  launch_lstm_step_fwd(have_labels ? LAB : bos.data_ptr<int64_t>(), have_labels ? L : 1,
+  launch_lstm_step_fwd(have_labels ? LABR : TokRows(bos.data_ptr<int64_t>()), have_labels ? L : 1,
                        PTAB,
                        state0.empty() ? nullptr : reinterpret_cast<uint16_t*>(h0.data_ptr()),
                        state0.empty() ? nullptr : c0.data_ptr<float>(), VG, VDIV, (int)R, (int)H, WHH, h_buf(0, 0),
                        c_buf(0, 0), hd_buf(0, 0), (int)H, (float)drop_p, RNG, key(0, 0),
-                       gates_buf(0, 0), st, nullptr, (int)cell);
+                       gates_buf(0, 0), st, nullptr, (int)cell, &sinit);
   for (int64_t l = 1; l < NL; ++l) upper_step(l, 0);
   // Steps t >= 0: ONE launch runs the vocab projection of step t together with
   // the recurrent GEMM of step t+1 (pre = h_t W_hh^T + vgate, layer 0), then
@@ -643,7 +674,7 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
     const int do_sample = choose && (mode == SEL_SAMPLE_H || mode == SEL_SS_H);
     const bool exp_t = save && store_exp && t > 0;  // step 0: fp16, converted below
     const int vflags = do_sample | ((choose && mode == SEL_GREEDY_H) ? 2 : 0) | (exp_t ? 16 : 0);
-    const int64_t* tgt = (have_labels && t + 1 < L) ? LAB + (t + 1) : nullptr;
+    const TokRows tgt = (have_labels && t + 1 < L) ? LABR.col(t + 1) : TokRows();
     // attention: the same launch also projects q_{t+1} = h_t W_q^T (extra
     // W_q tiles of the recurrent GEMM, no vgate add); the attention kernel then
     // adds each row's video term into pre before the combine's cell epilogue
@@ -760,27 +791,31 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
 std::vector<at::Tensor> featpool_backward(at::Tensor dout, at::Tensor out,
                                           std::vector<at::Tensor> xs,
                                           std::vector<at::Tensor> ws, double drop_p,
-                                          std::vector<at::Tensor> outs);
+                                          std::vector<at::Tensor> outs,
+                                          c10::optional<at::Tensor> idx, int64_t C);
 
-// vg_bwd (concat model, data parallelism with direct gradient slots): the
-// video-gate / FeatPool backward and the packed -> PyTorch row order of the
-// LSTM weight gradients done HERE instead of after the call, so W_ih's and
-// the FeatPool parameters' gradients are final shortly after the reverse loop
-// (a third early all-reduce slice, grad event 2):
+// vg_bwd (concat model with direct gradient slots): the video-gate / FeatPool
+// backward done HERE instead of after the call, so W_ih's and the FeatPool
+// parameters' gradients are final shortly after the reverse loop (a third
+// early all-reduce slice, grad event 2):
 //   {dst_ie, dst_hh (int64 row maps), W_ih slot (4H x (E + Fv)), W_hh slot
-//    (4H x H), W_ih (fp32 parameter), fc (FeatPool output, B x Fv),
+//    (4H x H), packed W_iv shadow (bf16), fc (FeatPool output, B x Fv),
 //    FeatPool weight slots x vg_nf, bias slots x vg_nf, inputs x vg_nf,
-//    weights x vg_nf}; vg_p the FeatPool dropout.
+//    weights x vg_nf(, fc as bf16: the forward's side output)}; vg_p the
+//    FeatPool dropout.  The packed -> PyTorch row order of layer 0's weight
+//    gradients: dw_slots (the weight-gradient reduce's row map).
 // C = A^T B over the first K rows of the bf16 row-major operands A (K x >= M)
 // and B (K x >= N) through the hand-written split-K kernel (kernels/wgrad.hip):
 // rows [0, M0) of C into C0 (row stride ldc0), rows [M0, M) into C1.  Returns
 // false (nothing launched) when the shapes do not fit the kernel.
 // al / db (optional, N = 512): also db[m] = sum_k al[k] A[k][m] (fused column
 // sums of the A tiles in LDS)
+// rmap (optional, M0 ints on the device): row m < M0 is stored as row rmap[m]
+// of C0 (< 0: dropped) -- the packed -> PyTorch gate order of a weight slot
 static bool wgrad_tn_into(const at::Tensor& A, int64_t lda, const at::Tensor& B, int64_t ldb,
                           int64_t M, int64_t N, int64_t K, float* C0, int64_t ldc0, int64_t M0,
                           float* C1, int64_t ldc1, hipStream_t st, const float* al = nullptr,
-                          float* db = nullptr) {
+                          float* db = nullptr, const int* rmap = nullptr) {
   if (A.scalar_type() != at::kBFloat16 || B.scalar_type() != at::kBFloat16 ||
       !wgrad_tn_ok(M, N, K, lda, ldb, A.data_ptr(), B.data_ptr()) || (db != nullptr && N != 512))
     return false;
@@ -791,7 +826,8 @@ static bool wgrad_tn_into(const at::Tensor& A, int64_t lda, const at::Tensor& B,
   WgradArgs g{reinterpret_cast<const uint16_t*>(A.data_ptr()), lda,
               reinterpret_cast<const uint16_t*>(B.data_ptr()), ldb, (int)M, (int)N, (int)K, S, 0,
               S > 1 ? ws.data_ptr<float>() : nullptr, C0, ldc0, (int)M0, C1, ldc1,
-              db != nullptr ? al : nullptr, db, ws_db.defined() ? ws_db.data_ptr<float>() : nullptr};
+              db != nullptr ? al : nullptr, db, ws_db.defined() ? ws_db.data_ptr<float>() : nullptr,
+              rmap};
   launch_wgrad_tn(g, st);
   return true;
 }
@@ -869,6 +905,28 @@ at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K)
   return C;
 }
 
+// test entry of the row-mapped store: row m of A[:K]^T B[:K] into row rmap[m]
+// of out (fp32, >= N columns, any row stride; rmap int32 (M), < 0 = dropped)
+void wgrad_tn_rows(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K, at::Tensor out,
+                   at::Tensor rmap) {
+  check_cuda(A, "A");
+  check_cuda(B, "B");
+  check_cuda(out, "out");
+  check_cuda(rmap, "rmap");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.stride(1) == 1 && B.stride(1) == 1 &&
+                  A.size(0) >= K && B.size(0) >= K && A.size(1) >= M && B.size(1) >= N,
+              "wgrad_tn_rows: operand shapes");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.stride(1) == 1 &&
+                  out.size(1) >= N && rmap.scalar_type() == at::kInt && rmap.is_contiguous() &&
+                  rmap.numel() == M,
+              "wgrad_tn_rows: out fp32 (rows, >= N), rmap int32 (M)");
+  TORCH_CHECK(rmap.max().item<int>() < out.size(0), "wgrad_tn_rows: rmap beyond the rows of out");
+  TORCH_CHECK(wgrad_tn_into(A, A.stride(0), B, B.stride(0), M, N, K, out.data_ptr<float>(),
+                            out.stride(0), M, nullptr, 0, cur_stream(), nullptr, nullptr,
+                            rmap.data_ptr<int>()),
+              "wgrad_tn_rows: shapes not supported (N a multiple of 128, 16-byte rows)");
+}
+
 // test entry of the fused form: {C (M x N), db (M)} with db[m] = sum_k al[k] A[k][m]
 std::vector<at::Tensor> wgrad_tn_colsum(at::Tensor A, at::Tensor B, at::Tensor al, int64_t M,
                                         int64_t N, int64_t K) {
@@ -901,7 +959,8 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
                                          at::Tensor fix_total, int64_t vgate_div,
                                          at::Tensor xw, std::vector<at::Tensor> vg_bwd,
                                          int64_t vg_nf, double vg_p, int64_t x_wait,
-                                         bool exp_zero_off) {
+                                         bool exp_zero_off, std::vector<at::Tensor> dw_slots,
+                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C) {
   const int64_t n_steps = logits16.size(0), R = logits16.size(1), ldl = logits16.size(2);
   const int64_t H4 = wx.size(0), H = H4 / 4, E = wx.size(1) - H, V = wlog.size(0);
   const int64_t T_sel = seq.size(1);
@@ -1514,9 +1573,12 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
   at::Tensor dvg;
   const bool vg_direct = !has_att && !vg_bwd.empty();
   if (vg_direct)
-    TORCH_CHECK(vg_nf >= 1 && (int64_t)vg_bwd.size() == 6 + 4 * vg_nf && NL == 1 && !has_s0,
+    TORCH_CHECK(vg_nf >= 1 &&
+                    ((int64_t)vg_bwd.size() == 6 + 4 * vg_nf ||
+                     (int64_t)vg_bwd.size() == 7 + 4 * vg_nf) &&
+                    NL == 1 && !has_s0,
                 "vg_bwd = {dst_ie, dst_hh, W_ih slot, W_hh slot, packed W_iv shadow, fc, FeatPool slots, "
-                "inputs, weights}");
+                "inputs, weights(, fc as bf16)}");
   std::vector<at::Tensor> vg_keep;  // (side-stream temporaries, released after the join)
   if (!has_att) {
     TORCH_CHECK(vgate_div >= 1 && R % vgate_div == 0, "vgate_div must divide the rows");
@@ -1549,14 +1611,20 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
       at::Tensor dvg_u = dvg16;
       at::Tensor dfc = at::empty({dvg.size(0), Fv}, f32);
       at::Tensor wiv16 = vg_bwd[4];
-      at::Tensor fc16 = vg_bwd[5].to(at::kBFloat16);
+      // (fc as bf16: the forward's FeatPool epilogue wrote it next to fc)
+      at::Tensor fc16 = (int64_t)vg_bwd.size() == 7 + 4 * vg_nf ? vg_bwd.back()
+                                                               : vg_bwd[5].to(at::kBFloat16);
+      TORCH_CHECK(fc16.scalar_type() == at::kBFloat16 && fc16.sizes() == vg_bwd[5].sizes() &&
+                      fc16.is_contiguous(),
+                  "vg_bwd: fc as bf16 must match fc");
       gemm_bf16_tuned(dfc, dvg_p16, false, wiv16, false, 24);
       at::Tensor wiv_slot = vg_bwd[2].narrow(1, E, Fv);
       gemm_bf16_tuned(wiv_slot, dvg16, true, fc16, false, 24);
       std::vector<at::Tensor> outs(vg_bwd.begin() + 6, vg_bwd.begin() + 6 + 2 * vg_nf);
       std::vector<at::Tensor> xs(vg_bwd.begin() + 6 + 2 * vg_nf, vg_bwd.begin() + 6 + 3 * vg_nf);
       std::vector<at::Tensor> wsv(vg_bwd.begin() + 6 + 3 * vg_nf, vg_bwd.begin() + 6 + 4 * vg_nf);
-      (void)featpool_backward(dfc, vg_bwd[5], xs, wsv, vg_p, outs);
+      // (vg_idx: the forward read its rows out of the resident tables by index)
+      (void)featpool_backward(dfc, vg_bwd[5], xs, wsv, vg_p, outs, vg_idx, vg_C);
       vg_keep = {dvg_u, dfc, dvg16, dvg_p16, fc16};
     }
     (void)hipEventRecord(aux.ev[5], side2.stream());
@@ -1568,6 +1636,34 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
   //    tiles in flight than one K = 35k GEMM), summed afterwards.
   at::Tensor dWx = at::empty({H4, E + H}, f32);
   at::Tensor dWq = has_att ? at::empty({A, H}, f32) : at::Tensor();
+  // dw_slots (direct gradient slots): {W_ih slot (G*H, >= E columns), W_hh slot
+  // (G*H, H), dst_ie, dst_hh (int64, G*H: packed row of each PyTorch row),
+  // inv_ie, inv_hh (int32, 4H: PyTorch row of each packed row, -1 = unused
+  // gate slot)}.  The split-K reduce (kernels/wgrad.hip) stores layer 0's dW_ie
+  // and dW_hh rows straight into the slots through the inverse maps; a shape
+  // the kernel does not take goes through dWx and a gather + copy instead.
+  const bool slot_direct = !dw_slots.empty();
+  if (slot_direct) {
+    TORCH_CHECK(dw_slots.size() == 6, "dw_slots = {W_ih slot, W_hh slot, dst_ie, dst_hh, inv_ie, inv_hh}");
+    const at::Tensor &s_ih = dw_slots[0], &s_hh = dw_slots[1];
+    for (const at::Tensor& t : dw_slots) check_cuda(t, "dw_slots");
+    TORCH_CHECK(s_ih.scalar_type() == at::kFloat && s_ih.dim() == 2 && s_ih.stride(1) == 1 &&
+                    s_ih.size(1) >= E && s_hh.scalar_type() == at::kFloat && s_hh.dim() == 2 &&
+                    s_hh.stride(1) == 1 && s_hh.size(1) == H && s_ih.size(0) == s_hh.size(0) &&
+                    s_ih.size(0) <= H4,
+                "dw_slots: fp32 W_ih (rows, >= E) / W_hh (rows, H) slots with unit column stride");
+    TORCH_CHECK(dw_slots[2].scalar_type() == at::kLong && dw_slots[3].scalar_type() == at::kLong &&
+                    dw_slots[2].numel() == s_ih.size(0) && dw_slots[3].numel() == s_hh.size(0),
+                "dw_slots: dst_ie / dst_hh int64, one entry per slot row");
+    TORCH_CHECK(dw_slots[4].scalar_type() == at::kInt && dw_slots[5].scalar_type() == at::kInt &&
+                    dw_slots[4].is_contiguous() && dw_slots[5].is_contiguous() &&
+                    dw_slots[4].numel() == H4 && dw_slots[5].numel() == H4,
+                "dw_slots: inv_ie / inv_hh int32 (4H)");
+  }
+  TORCH_CHECK(!vg_direct || slot_direct, "vg_bwd needs dw_slots (W_ih / W_hh slots and row maps)");
+  // (an initial state adds its own term onto dW_hh afterwards: through dWx)
+  const bool slot_map = slot_direct && !has_s0;
+  bool hh_in_slot = false, ie_in_slot = false;
   auto grouped_wgrad = [&](at::Tensor a_rows, at::Tensor b_rows, int64_t nsteps) {
     int64_t G = 1;  // steps per group: largest divisor <= 7
     for (int64_t g = 7; g >= 1; --g)
@@ -1582,10 +1678,15 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
   auto whh_grad = [&](hipStream_t ws) {  // (current stream: ws)
     if (n_steps > 1 && h_all.is_contiguous() &&
         wgrad_tn_into(dGx.narrow(0, R, (n_steps - 1) * R), KD, h_all, H, KD, H,
-                      (n_steps - 1) * R, dWx.data_ptr<float>() + E, E + H, H4,
-                      has_att ? dWq.data_ptr<float>() : nullptr, H, ws)) {
+                      (n_steps - 1) * R,
+                      slot_map ? dw_slots[1].data_ptr<float>() : dWx.data_ptr<float>() + E,
+                      slot_map ? dw_slots[1].stride(0) : E + H, H4,
+                      has_att ? dWq.data_ptr<float>() : nullptr, H, ws, nullptr, nullptr,
+                      slot_map ? dw_slots[5].data_ptr<int>() : nullptr)) {
       // (hand-written split-K MFMA kernel, kernels/wgrad.hip: rows [0, 4H) of
-      // [dG | dq]^T h_prev into dW_hh's columns of dWx, the dq rows into dW_q)
+      // [dG | dq]^T h_prev into dW_hh's columns of dWx -- or, through the row
+      // map, into W_hh's gradient slot --, the dq rows into dW_q)
+      hh_in_slot = slot_map;
     } else if (n_steps > 1) {
       at::Tensor wh;
       wh = grouped_wgrad(dGx.narrow(0, R, (n_steps - 1) * R),
@@ -1610,7 +1711,8 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
     (void)hipStreamWaitEvent(side.stream(), aux.ev[4], 0);
     c10::hip::HIPStreamGuard guard(side);
     whh_grad(side.stream());
-    if (vg_direct) vg_bwd[3].copy_(dWx.narrow(1, E, H).index_select(0, vg_bwd[1]));
+    if (slot_direct && !hh_in_slot)  // (a shape outside the kernel: gather + copy)
+      dw_slots[1].copy_(dWx.narrow(1, E, H).index_select(0, dw_slots[3]));
     (void)hipEventRecord(ev_done, side.stream());  // (joined below)
   }
 
@@ -1651,9 +1753,13 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
       if (V % g == 0 && V / g >= 512) { nk = g; break; }
     at::Tensor dWie = dWx.narrow(1, 0, E);
     if (emb.dim() == 2 && emb.stride(1) == 1 && S_tok.is_contiguous() &&
-        wgrad_tn_into(S_tok, H4, emb, emb.stride(0), H4, E, V, dWie.data_ptr<float>(), E + H, H4,
-                      nullptr, 0, st)) {
-      // (hand-written split-K MFMA kernel, kernels/wgrad.hip)
+        wgrad_tn_into(S_tok, H4, emb, emb.stride(0), H4, E, V,
+                      slot_map ? dw_slots[0].data_ptr<float>() : dWie.data_ptr<float>(),
+                      slot_map ? dw_slots[0].stride(0) : E + H, H4, nullptr, 0, st, nullptr, nullptr,
+                      slot_map ? dw_slots[4].data_ptr<int>() : nullptr)) {
+      // (hand-written split-K MFMA kernel, kernels/wgrad.hip; with direct slots
+      // the rows land in W_ih's token columns in PyTorch gate order)
+      ie_in_slot = slot_map;
     } else if (nk > 1 && emb.is_contiguous())
       at::sum_out(dWie,
                   at::bmm(S_tok.view({nk, V / nk, H4}).transpose(1, 2), emb.view({nk, V / nk, E}),
@@ -1663,10 +1769,11 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
       dWie.copy_(at::mm(S_tok.t(), emb, at::kFloat));
   }
   stamp(STAMP_BWD_TOKGEMM, st);
+  if (slot_direct && !ie_in_slot)  // (a shape outside the kernel: gather + copy)
+    dw_slots[0].narrow(1, 0, E).copy_(dWx.narrow(1, 0, E).index_select(0, dw_slots[2]));
   if (vg_direct) {
-    // W_ih's token columns (packed -> PyTorch rows) and, from the second side
+    // W_ih's token columns are in the slot (above) and, from the second side
     // stream, its video columns and the FeatPool gradients: slice 2 is final
-    vg_bwd[2].narrow(1, 0, E).copy_(dWx.narrow(1, 0, E).index_select(0, vg_bwd[0]));
     (void)hipStreamWaitEvent(st, aux.ev[5], 0);
     if (grad_ev) record_grad_event(aux.grad_ev[2], st, 2);
   }
@@ -1728,9 +1835,13 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
 // FeatPool (csrc/kernels/featpool.hip): xs[f] (rows, d_f), ws[f] (H, d_f),
 // bs[f] (H), all fp32 contiguous GPU tensors; returns the concatenated
 // (rows, F*H) output after ReLU and dropout (mask from rng slot 0).
+// idx (optional, int64 (n)): xs are then the resident tables (table rows * C,
+// d_f) and the call covers the rows idx[r / C] * C + r % C, r < n * C.
 static FeatPoolArgs featpool_args(const std::vector<at::Tensor>& xs,
                                   const std::vector<at::Tensor>& ws,
-                                  const std::vector<at::Tensor>& bs) {
+                                  const std::vector<at::Tensor>& bs,
+                                  const c10::optional<at::Tensor>& idx = c10::nullopt,
+                                  int64_t C = 1) {
   TORCH_CHECK(!xs.empty() && xs.size() <= FEATPOOL_MAX_F && ws.size() == xs.size() &&
                   (bs.empty() || bs.size() == xs.size()),
               "featpool: 1..", FEATPOOL_MAX_F, " modalities, one weight (and bias) each");
@@ -1738,6 +1849,18 @@ static FeatPoolArgs featpool_args(const std::vector<at::Tensor>& xs,
   a.nf = (int)xs.size();
   a.rows = (int)xs[0].size(0);
   a.H = (int)ws[0].size(0);
+  const int64_t x_rows = xs[0].size(0);
+  if (idx.has_value() && idx->defined()) {
+    check_cuda(*idx, "featpool idx");
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->dim() == 1 && idx->is_contiguous() &&
+                    idx->numel() > 0 && C >= 1 && x_rows > 0 && x_rows % C == 0 &&
+                    idx->numel() * C < (1LL << 31) && idx->device() == xs[0].device(),
+                "featpool: idx int64 (n) on the features' device, tables of (table rows * C) rows");
+    a.idx = idx->data_ptr<int64_t>();
+    a.C = (int)C;
+    a.n_table = (int)(x_rows / C);
+    a.rows = (int)(idx->numel() * C);
+  }
   TORCH_CHECK(a.H % 64 == 0, "featpool: output size must be a multiple of 64");
   for (int f = 0; f < a.nf; ++f) {
     const at::Tensor &x = xs[f], &w = ws[f];
@@ -1746,7 +1869,7 @@ static FeatPoolArgs featpool_args(const std::vector<at::Tensor>& xs,
     TORCH_CHECK(x.is_cuda(), "featpool x must be a GPU tensor");
     check_cuda(w, "featpool w");
     TORCH_CHECK(x.scalar_type() == at::kFloat && w.scalar_type() == at::kFloat && x.dim() == 2 &&
-                    w.dim() == 2 && x.size(0) == a.rows && w.size(0) == a.H &&
+                    w.dim() == 2 && x.size(0) == x_rows && w.size(0) == a.H &&
                     x.size(1) == w.size(1) && x.size(1) % 4 == 0 &&
                     (x.size(1) == 1 || x.stride(1) == 1) && x.stride(0) % 4 == 0 &&
                     x.stride(0) >= x.size(1) &&
@@ -1768,15 +1891,34 @@ static FeatPoolArgs featpool_args(const std::vector<at::Tensor>& xs,
 }
 
 at::Tensor featpool_forward(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
-                            std::vector<at::Tensor> bs, double drop_p, at::Tensor rng) {
+                            std::vector<at::Tensor> bs, double drop_p, at::Tensor rng,
+                            c10::optional<at::Tensor> idx, int64_t C) {
   TORCH_CHECK(bs.size() == xs.size(), "featpool: one bias per modality");
-  FeatPoolArgs a = featpool_args(xs, ws, bs);
+  FeatPoolArgs a = featpool_args(xs, ws, bs, idx, C);
   auto f32 = xs[0].options();
   at::Tensor wsp = at::empty({(int64_t)a.fwd_blocks * 64 * 64}, f32);
   at::Tensor out = at::empty({a.rows, (int64_t)a.nf * a.H}, f32);
-  launch_featpool_fwd(a, wsp.data_ptr<float>(), out.data_ptr<float>(), (float)drop_p,
+  launch_featpool_fwd(a, wsp.data_ptr<float>(), out.data_ptr<float>(), nullptr, (float)drop_p,
                       rng_ptr(rng), cur_stream());
   return out;
+}
+
+// {out fp32 (rows, F*H), out as bf16 (round to nearest even)}: FeatPool for
+// the gate GEMM that follows (bf16 operand, no conversion pass)
+std::vector<at::Tensor> featpool_forward16(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
+                                           std::vector<at::Tensor> bs, double drop_p,
+                                           at::Tensor rng, c10::optional<at::Tensor> idx,
+                                           int64_t C) {
+  TORCH_CHECK(bs.size() == xs.size(), "featpool: one bias per modality");
+  FeatPoolArgs a = featpool_args(xs, ws, bs, idx, C);
+  auto f32 = xs[0].options();
+  at::Tensor wsp = at::empty({(int64_t)a.fwd_blocks * 64 * 64}, f32);
+  at::Tensor out = at::empty({a.rows, (int64_t)a.nf * a.H}, f32);
+  at::Tensor out16 = at::empty({a.rows, (int64_t)a.nf * a.H}, f32.dtype(at::kBFloat16));
+  launch_featpool_fwd(a, wsp.data_ptr<float>(), out.data_ptr<float>(),
+                      reinterpret_cast<uint16_t*>(out16.data_ptr()), (float)drop_p, rng_ptr(rng),
+                      cur_stream());
+  return {out, out16};
 }
 
 // -> {dW_0 .. dW_{F-1}, db_0 .. db_{F-1}} given dL/d(out) and the forward's out;
@@ -1785,8 +1927,9 @@ at::Tensor featpool_forward(std::vector<at::Tensor> xs, std::vector<at::Tensor> 
 std::vector<at::Tensor> featpool_backward(at::Tensor dout, at::Tensor out,
                                           std::vector<at::Tensor> xs,
                                           std::vector<at::Tensor> ws, double drop_p,
-                                          std::vector<at::Tensor> outs) {
-  FeatPoolArgs a = featpool_args(xs, ws, {});
+                                          std::vector<at::Tensor> outs,
+                                          c10::optional<at::Tensor> idx, int64_t C) {
+  FeatPoolArgs a = featpool_args(xs, ws, {}, idx, C);
   check_cuda(dout, "featpool dout");
   check_cuda(out, "featpool out");
   TORCH_CHECK(dout.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat &&

@@ -62,6 +62,15 @@ __device__ __forceinline__ void fp_mfma_step(const float* As, const float* Bs, f
   }
 }
 
+// Row r of modality g.  With a row index the features are read where they lie
+// in the resident table (no gathered copy): frame r % C of table row idx[r / C],
+// the index clamped to the table so a bad value cannot leave it.
+__device__ __forceinline__ const float* fp_row(const FeatPoolArgs& a, const FeatPoolSeg& g, int r) {
+  if (a.idx == nullptr) return g.x + (int64_t)r * g.ld;
+  const int64_t v = min(max(a.idx[r / a.C], (int64_t)0), (int64_t)a.n_table - 1);
+  return g.x + (v * a.C + r % a.C) * g.ld;
+}
+
 // (row, col) of accumulator element r of lane `lane` in the 64x64 tile
 __device__ __forceinline__ int acc_row(int r, int lane, int wr) {
   return wr * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
@@ -86,14 +95,19 @@ __global__ __launch_bounds__(256) void featpool_fwd_partial_kernel(FeatPoolArgs 
   // each thread stages 2 float4 of A and of B per K step: tile row tid/8 + 32 i,
   // columns 4 (tid % 8)
   float4 ra[2], rb[2];
+  const float* xr[2];  // this thread's two feature rows (null: past the last row)
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int r = r0 + (tid >> 3) + 32 * i;
+    xr[i] = r < a.rows ? fp_row(a, g, r) : nullptr;
+  }
   auto load = [&](int k) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int row = (tid >> 3) + 32 * i, kk = k + 4 * (tid & 7);
       const bool kin = kk < kend;  // d % 4 == 0 (host check): a float4 is in or out
-      const int r = r0 + row;
-      ra[i] = (kin && r < a.rows) ? *reinterpret_cast<const float4*>(g.x + (int64_t)r * g.ld + kk)
-                                  : make_float4(0.f, 0.f, 0.f, 0.f);
+      ra[i] = (kin && xr[i] != nullptr) ? *reinterpret_cast<const float4*>(xr[i] + kk)
+                                        : make_float4(0.f, 0.f, 0.f, 0.f);
       rb[i] = kin ? *reinterpret_cast<const float4*>(g.w + (int64_t)(u0 + row) * g.d + kk)
                   : make_float4(0.f, 0.f, 0.f, 0.f);
     }
@@ -128,8 +142,11 @@ __global__ __launch_bounds__(256) void featpool_fwd_partial_kernel(FeatPoolArgs 
 }
 
 // ---- forward: sum of the K chunks + bias + ReLU + dropout -> (rows, F*H) ------
+// out16 (nullable): the same values as bf16 (round to nearest even), the
+// operand of the video-gate GEMM that follows
 __global__ __launch_bounds__(256) void featpool_fwd_epilogue_kernel(FeatPoolArgs a, const float* ws,
-                                                                    float* out, float drop_p,
+                                                                    float* out, uint16_t* out16,
+                                                                    float drop_p,
                                                                     const uint32_t* rng) {
   const int FH = a.nf * a.H;
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -160,6 +177,7 @@ __global__ __launch_bounds__(256) void featpool_fwd_epilogue_kernel(FeatPoolArgs
     y = keep ? y * (1.f / (1.f - drop_p)) : 0.f;
   }
   out[i] = y;
+  if (out16 != nullptr) out16[i] = f2bf(y);
 }
 
 // ---- backward: dW_f = dz^T x_f, db_f = sum_rows dz ----------------------------
@@ -194,7 +212,7 @@ __global__ __launch_bounds__(256) void featpool_bwd_kernel(FeatPoolArgs a, const
         const int64_t o = (int64_t)r * FH + f * a.H + u0 + c4;
         dy[i] = *reinterpret_cast<const float4*>(dout + o);
         yv[i] = *reinterpret_cast<const float4*>(outp + o);
-        if (k0 + c4 < g.d) xv[i] = *reinterpret_cast<const float4*>(g.x + (int64_t)r * g.ld + k0 + c4);
+        if (k0 + c4 < g.d) xv[i] = *reinterpret_cast<const float4*>(fp_row(a, g, r) + k0 + c4);
       }
     }
   };
@@ -246,13 +264,13 @@ void featpool_layout(FeatPoolArgs& a) {
   a.bwd_blocks = bblk;
 }
 
-void launch_featpool_fwd(const FeatPoolArgs& a, float* ws, float* out, float drop_p,
-                         const uint32_t* rng, hipStream_t stream) {
+void launch_featpool_fwd(const FeatPoolArgs& a, float* ws, float* out, uint16_t* out16,
+                         float drop_p, const uint32_t* rng, hipStream_t stream) {
   hipLaunchKernelGGL(featpool_fwd_partial_kernel, dim3(a.fwd_blocks), dim3(256), 0, stream, a, ws);
   post_launch("featpool_fwd_partial_kernel", stream);
   const int64_t n = (int64_t)a.rows * a.nf * a.H;
   hipLaunchKernelGGL(featpool_fwd_epilogue_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     stream, a, (const float*)ws, out, drop_p, rng);
+                     stream, a, (const float*)ws, out, out16, drop_p, rng);
   post_launch("featpool_fwd_epilogue_kernel", stream);
 }
 

@@ -38,14 +38,22 @@ __device__ __forceinline__ int xcd_remap_l(int bid, int nwg) {
 
 template <int BM, int STAGES>
 __global__ __launch_bounds__(256, 2) void lstm_step_fwd_kernel(
-    const int64_t* __restrict__ tok, int64_t tok_stride, const uint16_t* __restrict__ ptab,
+    TokRows tok, int64_t tok_stride, const uint16_t* __restrict__ ptab,
     const uint16_t* __restrict__ h_prev, const float* __restrict__ c_prev,
     const float* __restrict__ vgate, int vgate_div, int R, int H,
     const uint16_t* __restrict__ whh, uint16_t* __restrict__ h_out, float* __restrict__ c_out,
     uint16_t* __restrict__ hdrop_out, int ldh, float drop_p, const uint32_t* __restrict__ rng,
-    int step, uint16_t* __restrict__ gates_out, const int* __restrict__ row_map, int cell) {
+    int step, uint16_t* __restrict__ gates_out, const int* __restrict__ row_map, int cell,
+    StepInit init) {
   using LTile = Tile<BM, LB_N, STAGES>;
   extern __shared__ __attribute__((aligned(16))) char lds[];
+  // the decode's first launch: end-of-sequence flag words and row masks of the
+  // combines that follow it on the stream (grid-stride, a few words per thread)
+  if (init.n_flags > 0 || init.n_ones > 0) {
+    const int g0 = (int)blockIdx.x * 256 + (int)threadIdx.x, gn = (int)gridDim.x * 256;
+    for (int i = g0; i < init.n_flags; i += gn) init.flags[(int64_t)i * init.stride] = 0;
+    for (int i = g0; i < init.n_ones; i += gn) init.ones[i] = 1;
+  }
   const int n_nt = (4 * H) / LB_N, n_rt = (R + BM - 1) / BM;
   const int b = xcd_remap_l(blockIdx.x, n_nt * n_rt);
   const int nt = b / n_rt, rt = b % n_rt;
@@ -56,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void lstm_step_fwd_kernel(
   // layers of a stacked decoder have no token term: tok = ptab = null)
   int* s_tok = reinterpret_cast<int*>(lds + LTile::LDS_BYTES);
   if (threadIdx.x < BM)
-    s_tok[threadIdx.x] = tok ? (int)tok[(int64_t)min(r0 + (int)threadIdx.x, R - 1) * tok_stride] : 0;
+    s_tok[threadIdx.x] = tok.p ? (int)tok.at(min(r0 + (int)threadIdx.x, R - 1), tok_stride) : 0;
   __syncthreads();
 
   // Epilogue operands are gathered BEFORE the main loop, so their latency
@@ -821,13 +829,14 @@ void launch_lstm_step_bwd(const uint16_t* dg_next, const uint16_t* whhT, const f
 }
 
 // 128-row tiles x 64 packed gate columns, 3 LDS stages (72 KB, 2 blocks per CU)
-void launch_lstm_step_fwd(const int64_t* tok, int64_t tok_stride, const uint16_t* ptab,
+void launch_lstm_step_fwd(TokRows tok, int64_t tok_stride, const uint16_t* ptab,
                           const uint16_t* h_prev, const float* c_prev, const float* vgate,
                           int vgate_div, int R, int H, const uint16_t* whh, uint16_t* h_out,
                           float* c_out, uint16_t* hdrop_out, int ldh, float drop_p,
                           const uint32_t* rng, int step, uint16_t* gates_out, hipStream_t stream,
-                          const int* row_map, int cell) {
+                          const int* row_map, int cell, const StepInit* init) {
   constexpr int BM = 128, STAGES = 3;
+  const StepInit si = init ? *init : StepInit{};
   constexpr int LDS = Tile<BM, LB_N, STAGES>::LDS_BYTES + BM * 4;  // + staged token ids
   const int n_nt = (4 * H) / LB_N, n_rt = (R + BM - 1) / BM;
   static bool attr_set = false;
@@ -838,7 +847,7 @@ void launch_lstm_step_fwd(const int64_t* tok, int64_t tok_stride, const uint16_t
   }
   hipLaunchKernelGGL((lstm_step_fwd_kernel<BM, STAGES>), dim3(n_nt * n_rt), dim3(256), LDS,
                      stream, tok, tok_stride, ptab, h_prev, c_prev, vgate, vgate_div, R, H, whh,
-                     h_out, c_out, hdrop_out, ldh, drop_p, rng, step, gates_out, row_map, cell);
+                     h_out, c_out, hdrop_out, ldh, drop_p, rng, step, gates_out, row_map, cell, si);
   post_launch("lstm_step_fwd_kernel", stream);
 }
 

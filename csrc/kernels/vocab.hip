@@ -72,7 +72,7 @@ struct GroupStat {  // 32 bytes, one per (lane group, row) in LDS (exp_stage_off
 #define VOCAB_TR_PARAMS                                                                     \
   const uint16_t *__restrict__ hd, int ldh, int R, int H, const uint16_t *__restrict__ W,    \
       const float *__restrict__ bias, int V, uint16_t *__restrict__ logits16, int64_t ldl,   \
-      VocabPartial *__restrict__ part, const int64_t *__restrict__ tgt, int64_t tgt_stride, \
+      VocabPartial *__restrict__ part, TokRows tgt, int64_t tgt_stride,                     \
       int flags, float inv_temp, const uint32_t *__restrict__ rng, int step,                 \
       const float *__restrict__ eoff
 #define VOCAB_TR_ARGS \
@@ -115,7 +115,7 @@ __device__ __forceinline__ void vocab_tr_block(int bid, char* lds, VOCAB_TR_PARA
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const int r = min(r0 + wc * TL::WN + 32 * j + (lane & 31), R - 1);
-    tg[j] = tgt != nullptr ? (int)tgt[(int64_t)r * tgt_stride] : -1;
+    tg[j] = tgt.p != nullptr ? (int)tgt.at(r, tgt_stride) : -1;
     ec[j] = eoff != nullptr ? eoff[r] : 0.f;
   }
 
@@ -275,7 +275,7 @@ __device__ __forceinline__ void vocab_tr_block(int bid, char* lds, VOCAB_TR_PARA
         }
     }
     st.xt = -INFINITY;
-    if (tgt != nullptr) {
+    if (tgt.p != nullptr) {
       const int d = tg[j] - vb;
       const bool mine = d >= 0 && d < 32 * TM && (d & 4) == 0;
       const int kk = mine ? (d >> 5) * 16 + ((d >> 3) & 3) * 4 + (d & 3) : -1;
@@ -486,6 +486,7 @@ constexpr int CMB_LANES = 64, CMB_THREADS = 64;
 // line apart (see vocab_combine_kernel)
 constexpr int CMB_CNT_SLOTS = 64, CMB_CNT_STRIDE = 32;
 int combine_count_ints_per_step() { return CMB_CNT_SLOTS * CMB_CNT_STRIDE; }
+int combine_count_slots() { return CMB_CNT_SLOTS; }
 
 // Cell epilogue of the NEXT decode step, applied as soon as its input token
 // is chosen (see lstm_gemm.h): gates = pre + P[tok] -> i, f, g, o -> c, h.
@@ -602,7 +603,7 @@ __global__ __launch_bounds__(NT) void vocab_combine_kernel(
     const VocabPartial* __restrict__ part, int n_vt, int R, float* __restrict__ lse_out,
     int64_t* __restrict__ tok_out, int64_t tok_stride, float* __restrict__ g_sel,
     int64_t gsel_stride, float* __restrict__ g_xe, int64_t gxe_stride,
-    const int64_t* __restrict__ gt, int64_t gt_stride, int mode, float ss_prob,
+    TokRows gt, int64_t gt_stride, int mode, float ss_prob,
     const uint32_t* __restrict__ rng, int step, int* __restrict__ counts, int count_step,
     uint8_t* __restrict__ unfinished, CellArgs cell, int Rs) {
   __shared__ int s_nonzero;
@@ -656,7 +657,7 @@ __global__ __launch_bounds__(NT) void vocab_combine_kernel(
   int64_t gt_pre = 0;
   bool unf_pre = true;
   if (valid && sub == 0 && tok_out != nullptr) {
-    gt_pre = gt ? gt[(int64_t)r * gt_stride] : 0;
+    gt_pre = gt.p ? gt.at(r, gt_stride) : 0;
     unf_pre = unfinished == nullptr || unfinished[r] != 0;
   }
   // "some row emitted a non-EOS token at the previous step": CMB_CNT_SLOTS
@@ -879,8 +880,8 @@ static void launch_vocab_fwd_tr(const uint16_t* hd, int ldh, int R, int H, const
     attr_set = true;
   }
   hipLaunchKernelGGL((vocab_fwd_tr_kernel<BN, STAGES, OCC, TOPK>), dim3(n_vt * n_rt), dim3(256), LDS,
-                     stream, hd, ldh, R, H, W, bias, V, logits16, ldl, (VocabPartial*)part, tgt,
-                     tgt_stride, flags, inv_temp, rng, step, eoff);
+                     stream, hd, ldh, R, H, W, bias, V, logits16, ldl, (VocabPartial*)part,
+                     TokRows(tgt), tgt_stride, flags, inv_temp, rng, step, eoff);
   post_launch("vocab_fwd_tr_kernel", stream);
 }
 
@@ -927,7 +928,7 @@ int vocab_partial_bytes() { return (int)sizeof(VocabPartial); }
 
 void launch_vocab_combine(const void* part, int n_vt, int R, float* lse_out, int64_t* tok_out,
                           int64_t tok_stride, float* g_sel, int64_t gsel_stride, float* g_xe,
-                          int64_t gxe_stride, const int64_t* gt, int64_t gt_stride, int mode,
+                          int64_t gxe_stride, TokRows gt, int64_t gt_stride, int mode,
                           float ss_prob, const uint32_t* rng, int step, int* counts,
                           int count_step, uint8_t* unfinished, hipStream_t stream,
                           const CellLaunch* cl, int rows_per_step) {
@@ -965,7 +966,7 @@ void launch_vocab_combine(const void* part, int n_vt, int R, float* lse_out, int
 template <int BN, int STAGES, int OCC, class LT, int AV, bool TOPK = false, bool PH = false>
 static void launch_vocab_lstm_t(const uint16_t* hd, int ldh, int R, int H, const uint16_t* W,
                                 const float* bias, int V, uint16_t* logits16, int64_t ldl,
-                                void* part, const int64_t* tgt, int64_t tgt_stride, int flags,
+                                void* part, TokRows tgt, int64_t tgt_stride, int flags,
                                 float inv_temp, const uint32_t* rng, int step, const uint16_t* h_t,
                                 const uint16_t* whh, const float* vgate, int vdiv, float* pre,
                                 int NQ, float* q_out, hipStream_t stream, const float* eoff,
@@ -1003,7 +1004,7 @@ int vocab_part_slots(int V) { return (V + VT_V - 1) / VT_V; }
 
 int launch_vocab_lstm_fwd(const uint16_t* hd, int ldh, int R, int H, const uint16_t* W,
                           const float* bias, int V, uint16_t* logits16, int64_t ldl, void* part,
-                          const int64_t* tgt, int64_t tgt_stride, int flags, float inv_temp,
+                          TokRows tgt, int64_t tgt_stride, int flags, float inv_temp,
                           const uint32_t* rng, int step, const uint16_t* h_t, const uint16_t* whh,
                           const float* vgate, int vdiv, float* pre, hipStream_t stream, int NQ,
                           float* q_out, const float* eoff, const AttMfmaArgs* att, int pre_half) {
@@ -1107,7 +1108,7 @@ void launch_vocab_lstm_xe(const uint16_t* hd, int R, int H, const uint16_t* W, c
   }
   const XeCell x = xc != nullptr ? *xc : XeCell{};
   hipLaunchKernelGGL((vocab_lstm_xe_kernel<BN, STAGES, OCC>), dim3(grid), dim3(256), LDS, stream,
-                     hd, H, R, H, W, bias, V, logits16, ldl, (VocabPartial*)part, tgt, 1,
+                     hd, H, R, H, W, bias, V, logits16, ldl, (VocabPartial*)part, TokRows(tgt), 1,
                      /*flags: VF_EXP*/ 16, 1.f, rng, 0, nullptr, h_t, whh, vgate, vdiv, x, n_l);
   post_launch("vocab_lstm_xe_kernel", stream);
 }

@@ -24,7 +24,9 @@
 //   tiles go to an fp32 workspace and one reduce launch sums them in a fixed
 //   order (deterministic, bit-identical run to run) into the output rows --
 //   two row ranges with their own destinations and strides (the dW_hh / dW_q
-//   split of [dG | dq]^T h_prev);
+//   split of [dG | dq]^T h_prev), the first optionally through a destination
+//   row map (packed gate rows -> the PyTorch weight's rows, so the gradient
+//   lands in its bucket slot without a gather + copy pass);
 // * K need not be a multiple of 64: the buffer resource of each split ends at
 //   row K, so the DMA returns zeros for the rows past it;
 // * blocks are numbered split-major through the XCD remap, so the blocks of one
@@ -203,10 +205,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(WgradArgs g) {
         const int m = m0 + 64 * wr + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
         if (m >= g.M) continue;  // (ragged last m tile)
         float* dst;
-        if (g.S > 1)
+        if (g.S > 1) {
           dst = g.ws + ((int64_t)s * g.M + m) * g.N + n;
-        else
-          dst = m < g.M0 ? g.C0 + (int64_t)m * g.ldc0 + n : g.C1 + (int64_t)(m - g.M0) * g.ldc1 + n;
+        } else if (m < g.M0) {
+          const int md = g.rmap ? g.rmap[m] : m;  // (destination row map of C0)
+          if (md < 0) continue;
+          dst = g.C0 + (int64_t)md * g.ldc0 + n;
+        } else {
+          dst = g.C1 + (int64_t)(m - g.M0) * g.ldc1 + n;
+        }
         *dst = acc[i][j][r];
       }
     }
@@ -230,8 +237,20 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(WgradArgs g) {
     const float4 x = *reinterpret_cast<const float4*>(src + s * slab);
     a.x += x.x, a.y += x.y, a.z += x.z, a.w += x.w;
   }
-  float* dst = m < g.M0 ? g.C0 + (int64_t)m * g.ldc0 + c : g.C1 + (int64_t)(m - g.M0) * g.ldc1 + c;
-  *reinterpret_cast<float4*>(dst) = a;
+  float* dst;
+  if (m < g.M0) {
+    const int md = g.rmap ? g.rmap[m] : m;  // (destination row map of C0)
+    if (md < 0) return;
+    dst = g.C0 + (int64_t)md * g.ldc0 + c;
+  } else {
+    dst = g.C1 + (int64_t)(m - g.M0) * g.ldc1 + c;
+  }
+  // (a gradient-bucket slot starts wherever the parameters before it end: its
+  // rows need not be 16-byte aligned)
+  if ((reinterpret_cast<uintptr_t>(dst) & 15) == 0)
+    *reinterpret_cast<float4*>(dst) = a;
+  else
+    dst[0] = a.x, dst[1] = a.y, dst[2] = a.z, dst[3] = a.w;
 }
 
 }  // namespace

@@ -6,6 +6,32 @@
 
 namespace cst {
 
+// A column of int64 tokens read by row: row r is p[r * stride], or, where the
+// rows are taken out of a resident table through a row index (a batch's
+// caption rows of the label table: no gathered copy inside the step),
+// p[idx[r] * stride], idx[r] clamped to the table's n rows.  A plain pointer
+// converts to the unindexed form.
+struct TokRows {
+  const int64_t* p;
+  const int64_t* idx;  // nullable (n_rows of the consumer) int64 rows of the table
+  int64_t n;           // rows of the table behind p (with idx)
+  __host__ __device__ TokRows(const int64_t* p_ = nullptr, const int64_t* idx_ = nullptr,
+                              int64_t n_ = 0)
+      : p(p_), idx(idx_), n(n_) {}
+  __host__ __device__ int64_t at(int r, int64_t stride) const {
+    int64_t row = r;
+    if (idx != nullptr) {
+      row = idx[r];
+      row = row < 0 ? 0 : (row >= n ? n - 1 : row);
+    }
+    return p[row * stride];
+  }
+  // the same rows, c columns further (null stays null)
+  __host__ __device__ TokRows col(int64_t c) const {
+    return TokRows(p != nullptr ? p + c : nullptr, idx, n);
+  }
+};
+
 // beam.hip: fused beam step (LSE + candidate top-K + selection + next cell)
 struct BeamFusedArgs {
   const struct VocabPartial* part;  // (n_vt, R) tile partials of the vocab launch
@@ -144,11 +170,14 @@ bool att_mfma_fwd_ok(int vdiv, int C, int A, int H, int per_frame);
 void launch_att_mfma_fwd(const AttMfmaArgs& a, hipStream_t stream);
 // AttMfmaArgs::whole for a shape (1 with CSTCAP_ATT_WHOLE=1 where its LDS fits)
 int att_mfma_whole_default(int C, int H);
-// size of the end-of-sequence flag area per decode step (ints) of `counts`
+// size of the end-of-sequence flag area per decode step (ints) of `counts`,
+// and the flag words a combine reads in it: combine_count_slots() words per
+// step, combine_count_ints_per_step() / combine_count_slots() ints apart
 int combine_count_ints_per_step();
+int combine_count_slots();
 void launch_vocab_combine(const void* part, int n_vt, int R, float* lse_out, int64_t* tok_out,
                           int64_t tok_stride, float* g_sel, int64_t gsel_stride, float* g_xe,
-                          int64_t gxe_stride, const int64_t* gt, int64_t gt_stride, int mode,
+                          int64_t gxe_stride, TokRows gt, int64_t gt_stride, int mode,
                           float ss_prob, const uint32_t* rng, int step, int* counts, int count_step,
                           uint8_t* unfinished, hipStream_t stream, const CellLaunch* cell = nullptr,
                           int rows_per_step = 0);
@@ -164,7 +193,7 @@ void launch_vocab_combine(const void* part, int n_vt, int R, float* lse_out, int
 int vocab_part_slots(int V);
 int launch_vocab_lstm_fwd(const uint16_t* hd, int ldh, int R, int H, const uint16_t* W,
                            const float* bias, int V, uint16_t* logits16, int64_t ldl, void* part,
-                           const int64_t* tgt, int64_t tgt_stride, int flags, float inv_temp,
+                           TokRows tgt, int64_t tgt_stride, int flags, float inv_temp,
                            const uint32_t* rng, int step, const uint16_t* h_t, const uint16_t* whh,
                            const float* vgate, int vdiv, float* pre, hipStream_t stream,
                            int NQ = 0, float* q_out = nullptr, const float* eoff = nullptr,
@@ -250,12 +279,22 @@ void launch_vgrad_colsum(const uint16_t* E, int64_t ldl, int V, int64_t NR, cons
                          float* part, float* dblog, hipStream_t stream);
 
 // lstm.hip
-void launch_lstm_step_fwd(const int64_t* tok, int64_t tok_stride, const uint16_t* ptab,
+// Words the first launch of a decode initialises for the combines that follow
+// it on the stream (instead of a fill launch each): n_flags end-of-sequence
+// flag words, `stride` ints apart, set to 0; n_ones row-mask bytes set to 1.
+struct StepInit {
+  int* flags;
+  int n_flags, stride;
+  uint8_t* ones;
+  int n_ones;
+};
+void launch_lstm_step_fwd(TokRows tok, int64_t tok_stride, const uint16_t* ptab,
                           const uint16_t* h_prev, const float* c_prev, const float* vgate,
                           int vgate_div, int R, int H, const uint16_t* whh, uint16_t* h_out,
                           float* c_out, uint16_t* hdrop_out, int ldh, float drop_p,
                           const uint32_t* rng, int step, uint16_t* gates_out, hipStream_t stream,
-                          const int* row_map, int cell);  // row_map: h/c source row (beam)
+                          const int* row_map, int cell,  // row_map: h/c source row (beam)
+                          const StepInit* init = nullptr);
 
 // dg_next / dG rows have stride KD: 4H gate columns (+ A attention-query
 // columns, matched by extra whhT columns [W_hh^T | W_q^T] of width KD)
@@ -394,15 +433,21 @@ struct FeatPoolArgs {
   FeatPoolSeg s[FEATPOOL_MAX_F];
   int nf, rows, H;
   int fwd_blocks, bwd_blocks;
+  // optional row index: rows / C int64 table rows (clamped to [0, n_table)),
+  // one per group of C consecutive rows (the C frames of a video); row r of
+  // modality f is then x_f + (idx[r / C] * C + r % C) * ld.  null: row r.
+  const int64_t* idx;
+  int C, n_table;
 };
 struct FeatPoolGrads {
   float* dw[FEATPOOL_MAX_F];
   float* db[FEATPOOL_MAX_F];
 };
 void featpool_layout(FeatPoolArgs& a);  // fills blk0 / bblk0 / *_blocks
-// ws: fwd_blocks * 64 * 64 floats; out: (rows, nf * H)
-void launch_featpool_fwd(const FeatPoolArgs& a, float* ws, float* out, float drop_p,
-                         const uint32_t* rng, hipStream_t stream);
+// ws: fwd_blocks * 64 * 64 floats; out: (rows, nf * H); out16 (nullable): out
+// as bf16 (round to nearest even)
+void launch_featpool_fwd(const FeatPoolArgs& a, float* ws, float* out, uint16_t* out16,
+                         float drop_p, const uint32_t* rng, hipStream_t stream);
 void launch_featpool_bwd(const FeatPoolArgs& a, const float* dout, const float* out, float drop_p,
                          const FeatPoolGrads& gr, hipStream_t stream);
 
@@ -460,6 +505,9 @@ struct WgradArgs {
   const float* al;
   float* db;
   float* ws_db;
+  // destination row of each row [0, M0) in C0 (M0 ints, every value < the
+  // rows of C0; < 0: the row is not stored); null: row m goes to row m
+  const int* rmap;
 };
 bool wgrad_tn_ok(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, const void* A,
                  const void* B);

@@ -315,6 +315,13 @@ class CaptionLoader:
         idx = self._to_device(vids, rows) if rows is not None else self._to_device(vids)
         return Batch(self, vids, idx)
 
+    def feature_tables(self):
+        """The HBM-resident feature tables, one (videos, C, d_f) tensor per
+        modality (column slices of the concatenated table where there is one):
+        what a consumer that reads rows by index takes instead of a gathered
+        copy (:class:`IndexedFeats`)."""
+        return list(self.ds.device_tensors(self.device)['feats'])
+
     def gather(self, vid_t, rows_t=None, keys=None):
         """Device part of a batch from its index tensors: features, labels,
         masks (``nonzeros + 1``, ``dataloader.py:158-163``) and consensus
@@ -344,6 +351,50 @@ class CaptionLoader:
         return out
 
 
+class IndexedFeats:
+    """A batch's features as (resident tables, video index) for a consumer
+    that reads the rows by index (the fused FeatPool: no gathered copy inside
+    the step).  For everybody else it is the sequence of gathered (B, C, d_f)
+    tensors -- iterating, indexing or :meth:`gathered` makes the batch's one
+    gathered copy (``batch['feats']``) on the current stream."""
+
+    def __init__(self, batch, tables, index):
+        self._batch = batch
+        self.tables = tables  # [(videos, C, d_f)] per modality
+        self.index = index    # (B,) int64 rows of the tables
+
+    def gathered(self):
+        return self._batch['feats']
+
+    def __len__(self):
+        return len(self.tables)
+
+    def __iter__(self):
+        return iter(self.gathered())
+
+    def __getitem__(self, i):
+        return self.gathered()[i]
+
+
+class IndexedLabels:
+    """A batch's label rows as (resident (captions, L) table, caption-row
+    index) for a consumer that reads them by index (the fused decoder's
+    rollout: no gathered copy inside the step).  :meth:`gathered` is the
+    batch's one gathered copy (``batch['labels']``), made on the current
+    stream on first use."""
+
+    def __init__(self, batch, table, index):
+        self._batch = batch
+        self.table = table  # (captions, L) int64
+        self.index = index  # (R,) int64 rows of the table
+
+    def gathered(self):
+        return self._batch['labels']
+
+    def size(self, d):
+        return self.index.numel() if d == 0 else self.table.size(d)
+
+
 class LazyGather(dict):
     """The device part of a batch (``feats``, ``labels``, ``masks``,
     ``bcmrscores``), each gathered on its first access: a step that never
@@ -369,6 +420,30 @@ class LazyGather(dict):
         if k in self._DEVICE_KEYS:
             self._materialise(k)
         return super().__getitem__(k)
+
+    def feats_indexed(self):
+        """The features as :class:`IndexedFeats` (tables + this batch's video
+        index), without gathering anything; None once ``feats`` was gathered
+        (the caller may have modified the copy: use it)."""
+        if dict.__contains__(self, 'feats'):
+            return None
+        f = getattr(self, '_ifeats', None)
+        if f is None:
+            f = self._ifeats = IndexedFeats(self, self._loader.feature_tables(), self._idx[0])
+        return f
+
+    def labels_indexed(self):
+        """The labels as :class:`IndexedLabels` (the resident table + this
+        batch's caption rows), without gathering anything; None where the
+        split has no labels or ``labels`` was already gathered (use the
+        copy)."""
+        if len(self._idx) < 2 or dict.__contains__(self, 'labels'):
+            return None
+        lab = getattr(self, '_ilabels', None)
+        if lab is None:
+            table = self._loader.ds.device_tensors(self._loader.device)['labels']
+            lab = self._ilabels = IndexedLabels(self, table, self._idx[1])
+        return lab
 
     def get(self, k, default=None):
         if k in self._DEVICE_KEYS:

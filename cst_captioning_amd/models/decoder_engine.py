@@ -77,6 +77,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import _ext
+from ..utils.consts import const_tensor
 from ..utils.text import BOS
 
 SEL_GT, SEL_SAMPLE, SEL_GREEDY, SEL_SS = 0, 1, 2, 3
@@ -140,6 +141,14 @@ def gate_maps(rnn_type, H):
     return out
 
 
+def inverse_rows(dst, n):
+    """Inverse of a gather map ``dst`` (distinct rows of an n-row source):
+    int32 (n,), ``inv[dst[i]] = i`` and -1 where no row is taken."""
+    inv = torch.full((n,), -1, dtype=torch.int32, device=dst.device)
+    inv[dst] = torch.arange(dst.numel(), dtype=torch.int32, device=dst.device)
+    return inv
+
+
 class _DecoderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vgate, w_ih, w_hh, emb_w, logit_w, logit_b, att_gv, att_pre, att_wq,
@@ -148,6 +157,14 @@ class _DecoderFn(torch.autograd.Function):
                 *up_w):
         has_att = att_gv is not None
         dev = logit_b.device
+        # labels by index (data/dataset.py IndexedLabels): the resident label
+        # table + the call's rows of it; the kernels read the rows themselves
+        lab_idx = None
+        if labels is not None and not torch.is_tensor(labels):
+            if want_xe:  # (the XE backward and loss read the gathered rows)
+                labels = labels.gathered().contiguous()
+            else:
+                labels, lab_idx = labels.table, labels.index
         att = []
         if has_att:
             att = [att_gv.detach().float().contiguous(), att_pre.detach().float().contiguous(),
@@ -171,8 +188,9 @@ class _DecoderFn(torch.autograd.Function):
             labels if labels is not None else torch.empty(0, dtype=torch.long),
             bos if bos is not None else torch.empty(0, dtype=torch.long), R, T, modes, ss_prob,
             drop_p, temperature, rng, save, want_xe, use_counts, use_unfinished, att, eng.cell,
-            state0, eng.upper_operands(), store_exp, xe_rows)
+            state0, eng.upper_operands(), store_exp, xe_rows, lab_idx)
         ctx.xe_rows = xe_rows
+        ctx.lab_idx = lab_idx
         xw = torch.empty(0, device=dev)  # X = E W: engine.launch_x after the rollout
         seq, g_sel, g_xe, lse = outs[:4]
         ctx.save_dims = (R, T, vdiv, want_xe)
@@ -264,13 +282,20 @@ class _DecoderFn(torch.autograd.Function):
             g_sel = g_xe = None
             del logit_b_numel
         # input token of every step: it_0 = BOS / labels[:, 0], it_t = seq[:, t-1]
-        first = labels[:, :1] if labels is not None else bos.view(-1, 1)
+        lab_idx = ctx.lab_idx
+        if labels is None:
+            first = bos.view(-1, 1)
+        elif lab_idx is not None:  # labels: the resident table (R tokens gathered here)
+            first = labels[:, 0].index_select(0, lab_idx).view(-1, 1)
+            labels = None  # (no XE terms with indexed labels: nothing else reads them)
+        else:
+            first = labels[:, :1]
         toks = torch.cat([first, seq[:, :n_steps - 1]], 1).t().reshape(-1)
         # the vocab-head weight gradients go straight into their flat-bucket
         # slots (no autograd accumulate pass over the V x H gradient); under
         # data parallelism the backward also marks them final with an event
         # (engine set_grad_events), for the comm stream (parallel/dist.py)
-        direct = getattr(eng, 'direct_grad_slots', None)
+        direct = eng.direct_grad_slots
         if direct is not None:
             eng.check_direct_slots()
         if direct is not None:
@@ -286,14 +311,26 @@ class _DecoderFn(torch.autograd.Function):
         # concat model with direct slots: the video-gate / FeatPool backward
         # and the W_ih / W_hh row unpacking run inside the engine, right after
         # the reverse loop (third streamed DP slice)
-        vg_bwd, vg_nf, vg_p = [], 0, 0.0
+        vg_bwd, vg_nf, vg_p, vg_idx, vg_C = [], 0, 0.0, None, 1
         vg_ctx, ctx.vg_ctx = getattr(ctx, 'vg_ctx', None), None
         if (vg_ctx is not None and emb_direct and 'fp_w0' in direct and eng.layers == 1
                 and not ctx.state0 and eng.wiv is not None):
-            fc, xs, wsd, vg_p, vg_nf = vg_ctx.payload
+            fc, xs, wsd, vg_p, vg_nf, fc16, vg_idx, vg_C = vg_ctx.payload
             vg_bwd = ([eng.dst_ie, eng.dst_hh, direct['wih'], direct['whh'], eng.wiv, fc]
                       + [direct['fp_w%d' % f] for f in range(vg_nf)]
-                      + [direct['fp_b%d' % f] for f in range(vg_nf)] + list(xs) + list(wsd))
+                      + [direct['fp_b%d' % f] for f in range(vg_nf)] + list(xs) + list(wsd)
+                      + ([fc16] if fc16 is not None else []))
+        if direct is not None:
+            # does this backward overwrite EVERY direct slot?  (vg_bwd: the
+            # video columns and the FeatPool slots too; the exp-store form)
+            # The bucket's narrowed zero fill relies on it (trainer / dist.py).
+            eng.note_backward(bool(vg_bwd) and ctx.store_exp)
+        # layer 0's dW_ie / dW_hh: the weight-gradient reduce stores them in
+        # the slots' (PyTorch) gate order itself (no gather + copy afterwards)
+        dw_slots = []
+        if emb_direct:
+            dw_slots = [direct['wih'], direct['whh'], eng.dst_ie, eng.dst_hh, eng.inv_ie,
+                        eng.inv_hh]
         # the operand preparation above (token rows, contiguous gradients)
         # needs no X; it runs while the X stream still computes (3.362-3.402
         # vs 3.400-3.418 ms per step waiting first, profiles/r5/tail/), and so
@@ -306,7 +343,7 @@ class _DecoderFn(torch.autograd.Function):
             ctx.drop_p, ctx.rng, out_w, out_b, comm, att, out_emb, ds_bias, eng.cell,
             ctx.state0, eng.upper_operands(ctx.up_saved), ctx.logit_b, eng.exp_fix_rows,
             vdiv, xw if ctx.store_exp else empty, vg_bwd, vg_nf, float(vg_p),
-            0 if x_ev is None else int(x_ev.cuda_event), ctx.xe_rows)
+            0 if x_ev is None else int(x_ev.cuda_event), ctx.xe_rows, dw_slots, vg_idx, vg_C)
         ctx.logit_b = None
         ctx.up_saved = None
         d_up = []
@@ -328,21 +365,15 @@ class _DecoderFn(torch.autograd.Function):
             d_emb = None
         E = eng.E
         # packed gate rows -> the PyTorch weights' rows (unused slots dropped)
-        if not vg_bwd:
-            d_ie = dWx[:, :E].index_select(0, eng.dst_ie)
-            d_hh = dWx[:, E:].index_select(0, eng.dst_hh)
         w_ih_shape, emb_shape = ctx.shapes
-        if vg_bwd:  # (written by the engine)
+        if dw_slots:  # (written by the engine: W_ih's token columns and W_hh)
             d_wih = d_whh = None
-            vg_ctx.done = True  # the video-gate node's own backward is a no-op
-        elif emb_direct:
-            direct['wih'][:, :E].copy_(d_ie)
-            direct['whh'].copy_(d_hh)
-            d_wih = d_whh = None
+            if vg_bwd:
+                vg_ctx.done = True  # the video-gate node's own backward is a no-op
         else:
             d_wih = torch.zeros(w_ih_shape, dtype=torch.float32, device=dWx.device)
-            d_wih[:, :E] = d_ie
-            d_whh = d_hh
+            d_wih[:, :E] = dWx[:, :E].index_select(0, eng.dst_ie)
+            d_whh = dWx[:, E:].index_select(0, eng.dst_hh)
         if ctx.has_att:
             d_gv, d_pre, d_wa, d_ba, d_wq = res[5:10]
             d_wa, d_ba = d_wa.view(ctx.att_shapes[0]), d_ba.view(ctx.att_shapes[1])
@@ -402,7 +433,18 @@ class DecoderEngine:
         self.gates = G
         (self.src_ie, self.dst_ie, self.slots_ie), (self.src_hh, self.dst_hh, self.slots_hh) = \
             [(a.to(dev), b.to(dev), c) for a, b, c in gate_maps(model.rnn_type, H)]
+        # inverse of dst (int32, 4H: PyTorch row of each packed row, -1 in an
+        # unused gate slot): the destination row map of the weight-gradient
+        # reduce, which stores dW_ie / dW_hh straight into their gradient slots
+        self.inv_ie, self.inv_hh = [inverse_rows(d, 4 * H) for d in (self.dst_ie, self.dst_hh)]
         self.model = model
+        # direct gradient slots (set_direct_slots) and the narrowed zero fill
+        self.direct_grad_slots = None
+        self.direct_params = None
+        self.direct_armed = False
+        self._video_slots_ok = False
+        self._last_bwd_covered = False   # the last fused backward overwrote every slot
+        self.refill_direct_slots = None  # the bucket's zero_overwritten (trainer)
         # bf16 shadow weights read by the kernels.  Persistent buffers, updated
         # IN PLACE (by the fused Adam pass, or refresh_weights()), so a captured
         # HIP graph always reads the live weights.
@@ -622,6 +664,33 @@ class DecoderEngine:
     def arm_direct_slots(self):
         self.direct_armed = True
 
+    def direct_slots_covered(self):
+        """For the gradient bucket's narrowed zero fill: will the coming
+        step's fused backward OVERWRITE every registered slot?  Yes only for
+        the configuration whose backward writes all of them inside the engine
+        (one-layer concat model without attention: ``vg_bwd``), and only once
+        a backward of this engine has actually done so -- the first step of a
+        run, and the step after any backward that took another path, get the
+        full fill.  A step that was promised coverage and takes another path
+        after all is caught by :meth:`note_backward`.  Two consequences: a
+        step captured into a HIP graph right after a full-fill step keeps the
+        narrowed fill only if that step's backward was covered (the trainer
+        runs every new schedule eagerly once before capturing it, so the
+        capture sees a covered predecessor); and a step that calls zero_grad()
+        but never runs the fused backward leaves the PREVIOUS step's gradients
+        in the direct slots -- the trainer always runs it."""
+        return bool(self._last_bwd_covered and not self.attention
+                    and not self.standard and self.layers == 1 and self.wiv is not None)
+
+    def note_backward(self, covered):
+        """Called by the fused backward before it writes anything: ``covered``
+        = this backward overwrites every direct slot.  If not, and the bucket
+        skipped their zero fill for this step, zero them now (autograd is
+        about to accumulate into some of them)."""
+        self._last_bwd_covered = bool(covered)
+        if not covered and self.refill_direct_slots is not None:
+            self.refill_direct_slots()
+
     def check_direct_slots(self):
         """The fused backward OVERWRITES the gradient slots: one backward per
         zero_grad(), and the slots must still be the parameters' .grad."""
@@ -641,7 +710,7 @@ class DecoderEngine:
         """For the FeatPool / video-gate backward of the same pass (it runs
         after the decoder's): the direct slots, once, if the decoder backward
         verified them and the FeatPool parameters have slots too."""
-        ok = getattr(self, '_video_slots_ok', False)
+        ok = self._video_slots_ok
         self._video_slots_ok = False
         d = self.direct_grad_slots
         if not ok or d is None or 'fp_w0' not in d:
@@ -680,12 +749,25 @@ class DecoderEngine:
             h = torch.tanh(a)
         return h, h
 
+    def reads_by_index(self, model, feats):
+        """True when this engine's FeatPool reads ``feats`` (a batch's
+        IndexedFeats) out of the resident tables by index -- the fused FeatPool
+        node of the concat / temporal-attention model.  Everything else takes
+        the gathered copy."""
+        from ..ops.featpool import by_index, fused_ok
+        if self.standard or self.manet or by_index(feats) is None:
+            return False
+        t = feats.tables
+        return bool(fused_ok(model.feat_pool, t)
+                    and (t[0].dim() == 3 if self.attention else t[0].size(1) == 1))
+
     def _vgate(self, model, feats, expand):
         if self.standard:  # no per-step video term
             B = feats[0].size(0)
             return model.logit.bias.new_zeros(B, 4 * self.H), B
-        from ..ops.featpool import featpool_vgate, fused_ok
-        if fused_ok(model.feat_pool, feats) and feats[0].size(1) == 1:
+        from ..ops.featpool import featpool_vgate, fused_ok, probe
+        pf = probe(feats)  # (an indexed batch: its tables, nothing is gathered)
+        if fused_ok(model.feat_pool, pf) and pf[0].size(1) == 1:
             vg = featpool_vgate(self, model, feats)  # one node: FeatPool + gate term
             return vg, vg.size(0)
         fc = self._encode(model, feats)  # (B, F*H), FeatPool dropout in train mode
@@ -731,8 +813,9 @@ class DecoderEngine:
         if self.manet:
             return self._manet_inputs(model, feats)
         ta = model.temporal_att
-        from ..ops.featpool import att_inputs, fused_ok
-        if fused_ok(model.feat_pool, feats) and feats[0].dim() == 3:
+        from ..ops.featpool import att_inputs, fused_ok, probe
+        pf = probe(feats)  # (an indexed batch: its tables, nothing is gathered)
+        if fused_ok(model.feat_pool, pf) and pf[0].dim() == 3:
             # one node: FeatPool + one bf16 GEMM for Gv and P (ops/featpool.py;
             # att8 4.597 / 4.584 vs 4.776 / 4.780 ms per step with the two fp32
             # Linears below and their autograd backward, profiles/r5/README_r5.md)
@@ -771,7 +854,8 @@ class DecoderEngine:
             bos = None
         else:
             T = model.seq_length - 1
-            bos = torch.full((R,), BOS, dtype=torch.long, device=model.logit.bias.device)
+            # (a cached constant: no fill launch per decode)
+            bos = const_tensor('bos', (R,), BOS, torch.long, model.logit.bias.device)
         drop_p = model.drop_prob_lm if (model.training and drop) else 0.0
         m = model
         ws = (m.core.rnn.weight_ih_l0, m.core.rnn.weight_hh_l0, m.embed.weight, m.logit.weight,
@@ -784,7 +868,8 @@ class DecoderEngine:
         save = want_full or (torch.is_grad_enabled() and any(t.requires_grad for t in diff_in))
         self.ensure_ptab()
         return _DecoderFn.apply(vg, *ws, *att, h0, c0, self,
-                                labels.contiguous() if labels is not None else None, bos, R, T,
+                                labels.contiguous() if torch.is_tensor(labels) else labels, bos, R,
+                                T,
                                 modes, float(ss_prob), float(drop_p), float(temperature),
                                 self._rng(m.logit.bias.device), S, want_xe, use_counts,
                                 use_unfinished, save, want_full, *ups)

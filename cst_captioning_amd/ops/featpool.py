@@ -12,6 +12,7 @@ distribution-identical to ``nn.Dropout``.
 import torch
 
 from .. import _ext
+from ..utils.consts import const_tensor
 
 
 def fused_ok(pool, feats):
@@ -34,6 +35,37 @@ def _rows(f):
     if x.stride(-1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
         x = x.contiguous()
     return x
+
+
+def by_index(feats):
+    """(table rows [(videos * C, d_f)], video index, C) when ``feats`` is a
+    batch's :class:`~cst_captioning_amd.data.dataset.IndexedFeats` whose tables
+    the kernels can read in place (GPU fp32 rows with a unit column stride and
+    16-byte alignment); else None -- the caller uses the gathered tensors."""
+    tabs, idx = getattr(feats, 'tables', None), getattr(feats, 'index', None)
+    if not tabs or idx is None or not idx.is_cuda or idx.dtype != torch.long or idx.dim() != 1:
+        return None
+    if any(not t.is_cuda or t.dtype != torch.float32 or t.dim() not in (2, 3) for t in tabs):
+        return None
+    xs = [_rows(t) for t in tabs]
+    if any(x.data_ptr() != t.data_ptr() for x, t in zip(xs, tabs)):  # (a copy: no table)
+        return None
+    return xs, idx.contiguous(), (tabs[0].size(1) if tabs[0].dim() == 3 else 1)
+
+
+def probe(feats):
+    """Tensors that stand for ``feats`` in shape / dtype checks, without
+    gathering an indexed batch whose tables the kernels read in place."""
+    return feats.tables if by_index(feats) is not None else feats
+
+
+def _operands(feats):
+    """(xs, idx, C) of a fused FeatPool call: the resident tables and the
+    batch's index where ``feats`` brings them, else the gathered rows."""
+    tabs = by_index(feats)
+    if tabs is not None:
+        return tabs
+    return [_rows(f) for f in feats], None, (feats[0].size(1) if feats[0].dim() == 3 else 1)
 
 
 class _FeatPoolFn(torch.autograd.Function):
@@ -84,13 +116,21 @@ class _FeatPoolVgateFn(torch.autograd.Function):
     zero-fill / accumulate passes), else returned."""
 
     @staticmethod
-    def forward(ctx, eng, p, rng, nf, record, *args):
+    def forward(ctx, eng, p, rng, nf, record, idx, C, *args):
+        # idx (None or int64 (B,)): xs are the resident tables, read by index
         xs, ws, bs, w_ih = args[:nf], args[nf:2 * nf], args[2 * nf:3 * nf], args[3 * nf]
         wsd = [w.detach() for w in ws]
-        fc = _ext.ops().featpool_forward(list(xs), wsd, [b.detach() for b in bs], p, rng)
         w_iv = w_ih.detach()[:, eng.E:]
         wiv = getattr(eng, 'wiv', None)
-        if fc.is_cuda and wiv is not None:
+        fc16 = None
+        if xs[0].is_cuda and wiv is not None:
+            # (the epilogue writes fc as fp32 and as the GEMM's bf16 operand)
+            fc, fc16 = _ext.ops().featpool_forward16(list(xs), wsd, [b.detach() for b in bs], p,
+                                                     rng, idx, C)
+        else:
+            fc = _ext.ops().featpool_forward(list(xs), wsd, [b.detach() for b in bs], p, rng,
+                                             idx, C)
+        if fc16 is not None:
             # bf16 operands (W_iv: the engine's packed shadow, rows already in
             # packed gate order, so the product IS the packed gate term), fp32
             # accumulate and output, the measured hipBLASLt choice
@@ -99,15 +139,16 @@ class _FeatPoolVgateFn(torch.autograd.Function):
             # (profiles/r6/steps_xe_after_fixes.txt); the decoder's other input
             # terms are bf16 products too
             vg = torch.empty(fc.size(0), wiv.size(0), device=fc.device)
-            _ext.ops().gemm_bf16_tuned(vg, fc.to(torch.bfloat16), False, wiv, True)
+            _ext.ops().gemm_bf16_tuned(vg, fc16, False, wiv, True)
         else:
             vg = eng.pack_rows(torch.mm(fc, w_iv.t()), eng.src_ie, 1)
         ctx.eng, ctx.p, ctx.nf, ctx.wih_shape = eng, p, nf, w_ih.shape
+        ctx.idx, ctx.C = idx, C
         ctx.save_for_backward(fc, *xs, *wsd)
         # the decoder forward that consumes vg takes these, so its backward
         # can run this node's backward inside the engine (vg_bwd); only when
         # this node is recorded for a backward (no hand-off from eval / beam)
-        ctx.handoff = VgHandoff((fc, list(xs), wsd, p, nf), vg) if record else None
+        ctx.handoff = VgHandoff((fc, list(xs), wsd, p, nf, fc16, idx, C), vg) if record else None
         eng._vg_pending = ctx.handoff
         return vg
 
@@ -119,7 +160,7 @@ class _FeatPoolVgateFn(torch.autograd.Function):
             # the decoder backward already ran this node's backward (vg_bwd)
             # and wrote W_ih's video columns and the FeatPool gradient slots
             eng.take_video_slots()
-            return (None,) * (5 + 4 * nf)
+            return (None,) * (7 + 4 * nf)
         fc, *rest = ctx.saved_tensors
         xs, ws = list(rest[:nf]), list(rest[nf:])
         E = eng.E
@@ -131,12 +172,12 @@ class _FeatPoolVgateFn(torch.autograd.Function):
             torch.mm(dvg_u.t(), fc, out=direct['wih'][:, E:])
             outs = [direct['fp_w%d' % f] for f in range(nf)] + \
                    [direct['fp_b%d' % f] for f in range(nf)]
-            _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, outs)
-            return (None,) * (5 + 4 * nf)
+            _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, outs, ctx.idx, ctx.C)
+            return (None,) * (7 + 4 * nf)
         d_wih = fc.new_zeros(ctx.wih_shape)
         d_wih[:, E:] = dvg_u.t() @ fc
-        g = _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, [])
-        return (None,) * (5 + nf) + tuple(g[:nf]) + tuple(g[nf:]) + (d_wih,)
+        g = _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, [], ctx.idx, ctx.C)
+        return (None,) * (7 + nf) + tuple(g[:nf]) + tuple(g[nf:]) + (d_wih,)
 
 
 class _AttInputsFn(torch.autograd.Function):
@@ -152,21 +193,23 @@ class _AttInputsFn(torch.autograd.Function):
     :class:`_FeatPoolVgateFn`), else returned."""
 
     @staticmethod
-    def forward(ctx, eng, p, rng, nf, C, *args):
+    def forward(ctx, eng, p, rng, nf, C, idx, *args):
+        # idx (None or int64 (B,)): xs are the resident tables, read by index
         xs, ws, bs = args[:nf], args[nf:2 * nf], args[2 * nf:3 * nf]
         w_ih, wf, bf = args[3 * nf:3 * nf + 3]
         wsd = [w.detach() for w in ws]
-        fc = _ext.ops().featpool_forward(list(xs), wsd, [b.detach() for b in bs], p, rng)
+        fc, fc16 = _ext.ops().featpool_forward16(list(xs), wsd, [b.detach() for b in bs], p, rng,
+                                                 idx, C)
         E, G4, A = eng.E, w_ih.size(0), wf.size(0)
         wcat = torch.empty(G4 + A, fc.size(1), dtype=torch.bfloat16, device=fc.device)
         wcat[:G4].copy_(w_ih.detach()[:, E:])
         wcat[G4:].copy_(wf.detach())
-        fc16 = fc.to(torch.bfloat16)
         y = torch.mm(fc16, wcat.t(), out_dtype=torch.float32)  # (N * C, 4H + A)
-        B = xs[0].size(0) // C
+        B = fc.size(0) // C
         gv = eng.pack_rows(y[:, :G4], eng.src_ie, 1).view(B, C, -1)
         pre = (y[:, G4:] + bf.detach()).view(B, C, A)
         ctx.eng, ctx.p, ctx.nf, ctx.wih_shape, ctx.G4 = eng, p, nf, w_ih.shape, G4
+        ctx.idx, ctx.C = idx, C
         ctx.save_for_backward(fc, fc16, wcat, *xs, *wsd)
         return gv, pre
 
@@ -197,12 +240,12 @@ class _AttInputsFn(torch.autograd.Function):
             torch.mm(dyt[:G4], fc16, out_dtype=torch.float32, out=direct['wih'][:, E:])
             outs = [direct['fp_w%d' % f] for f in range(nf)] + \
                    [direct['fp_b%d' % f] for f in range(nf)]
-            _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, outs)
-            return (None,) * (5 + 3 * nf) + (None, dwf, dbf)
+            _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, outs, ctx.idx, ctx.C)
+            return (None,) * (6 + 3 * nf) + (None, dwf, dbf)
         d_wih = fc.new_zeros(ctx.wih_shape)
         d_wih[:, E:] = torch.mm(dyt[:G4], fc16, out_dtype=torch.float32)
-        g = _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, [])
-        return (None,) * (5 + nf) + tuple(g[:nf]) + tuple(g[nf:]) + (d_wih, dwf, dbf)
+        g = _ext.ops().featpool_backward(dfc, fc, xs, ws, ctx.p, [], ctx.idx, ctx.C)
+        return (None,) * (6 + nf) + tuple(g[:nf]) + tuple(g[nf:]) + (d_wih, dwf, dbf)
 
 
 def att_inputs(eng, model, feats):
@@ -212,11 +255,10 @@ def att_inputs(eng, model, feats):
     pool = model.feat_pool
     lins = [m[0] for m in pool.feat_list]
     p = float(pool.feat_list[0][2].p) if pool.training else 0.0
-    dev = feats[0].device
-    rng = _seeds(p, dev)
-    xs = [_rows(f) for f in feats]
+    xs, idx, C = _operands(feats)
+    rng = _seeds(p, xs[0].device)
     ta = model.temporal_att
-    return _AttInputsFn.apply(eng, p, rng, len(xs), feats[0].size(1), *xs, *[l.weight for l in lins],
+    return _AttInputsFn.apply(eng, p, rng, len(xs), C, idx, *xs, *[l.weight for l in lins],
                               *[l.bias for l in lins], model.core.rnn.weight_ih_l0,
                               ta.f_feat.weight, ta.f_feat.bias)
 
@@ -228,8 +270,8 @@ SEED_SOURCE = None
 
 
 def _seeds(p, dev):
-    if p <= 0:
-        return torch.zeros(2, dtype=torch.int32, device=dev)
+    if p <= 0:  # (never read: a cached constant, no fill launch per pass)
+        return const_tensor('seeds0', (2,), 0, torch.int32, dev)
     if SEED_SOURCE is not None:
         return SEED_SOURCE(dev)
     return torch.randint(0, 2 ** 31 - 1, (2,), dtype=torch.int32, device=dev)
@@ -241,12 +283,11 @@ def featpool_vgate(eng, model, feats):
     pool = model.feat_pool
     lins = [m[0] for m in pool.feat_list]
     p = float(pool.feat_list[0][2].p) if pool.training else 0.0
-    dev = feats[0].device
-    rng = _seeds(p, dev)
-    xs = [_rows(f) for f in feats]
+    xs, idx, C = _operands(feats)
+    rng = _seeds(p, xs[0].device)
     params = [l.weight for l in lins] + [l.bias for l in lins] + [model.core.rnn.weight_ih_l0]
     record = torch.is_grad_enabled() and any(t.requires_grad for t in params + xs)
-    return _FeatPoolVgateFn.apply(eng, p, rng, len(xs), record, *xs, *params)
+    return _FeatPoolVgateFn.apply(eng, p, rng, len(xs), record, idx, C, *xs, *params)
 
 
 def featpool(pool, feats):

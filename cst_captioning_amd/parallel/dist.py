@@ -7,12 +7,14 @@ layer adds DP for one node of MI355X GPUs, one process per GPU:
   C2  the whole gradient as ONE flat bucket, all-reduced in at most three
       large slices ordered by when the backward finalises them
       (:meth:`FlatGradBucket.all_reduce`): the vocabulary head (logit W, b:
-      final after its dW GEMM, which runs under the reverse LSTM loop), the
-      embedding (final after its GEMM in the post-loop tail), then the rest.
-      The fused backward marks the first two with events (external
-      event-record nodes inside a captured HIP graph); the comm stream (high
-      priority: a hardware queue of its own) waits on the step-start event and
-      on them -- never on the whole replay -- and their all-reduces run while
+      final after its dW GEMM, which starts on a side stream right after the
+      persistent reverse LSTM loop, not under it), the embedding (final after
+      its GEMM in the post-loop tail), W_ih + FeatPool (concat model), then the
+      rest.  The fused backward marks the streamed slices with events (external
+      event-record nodes inside a captured HIP graph); the comm stream (normal
+      priority by default: a high-priority queue measured 1.7x slower per
+      replayed step, :meth:`FlatGradBucket.set_groups`) waits on the step-start
+      event and on them -- never on the whole replay -- and their all-reduces run while
       the rest of the backward does -- eager RCCL, nothing captured.  Large slices are
       what a point-to-point xGMI ring moves at full per-link bandwidth
       (~20 M params = 84 MB fp32).  --dp_update sharded: reduce-scatter ->
@@ -180,6 +182,11 @@ class FlatGradBucket:
         self._counts = None
         self.events_ok = False
         self.on_zero = None
+        # narrowed zero fill (set_overwritten)
+        self._covered = None
+        self._zero_pieces = []
+        self._over_pieces = []
+        self.narrow_zeroed = False
         if not self.params:
             raise ValueError('no trainable parameters')
         dev = self.params[0].device
@@ -215,8 +222,49 @@ class FlatGradBucket:
         flag (0-dim bool device tensor, no host sync)."""
         return self.flag[0] > 0
 
+    def set_overwritten(self, ranges, covered):
+        """``ranges``: (offset, numel) pieces of the buffer that a fused
+        backward OVERWRITES (the engine's direct gradient slots) instead of
+        accumulating into; ``covered()``: true when the coming step's backward
+        is known to overwrite every one of them.  :meth:`zero_grad` then zeroes
+        only the rest of the buffer (everything autograd accumulates into, the
+        status slot and the padding), adjacent pieces merged into as few fills
+        as possible.  Whoever answers ``covered()`` must call
+        :meth:`zero_overwritten` before a backward that turns out not to
+        overwrite them after all.  A step that never runs that backward after
+        a narrowed fill finds the previous step's gradients in those ranges."""
+        keep, at = [], 0
+        for off, n in sorted(ranges):
+            if off < at:
+                raise ValueError('overlapping overwritten ranges')
+            if off > at:
+                keep.append((at, off))
+            at = off + n
+        if at > self.grad.numel():
+            raise ValueError('overwritten range beyond the buffer')
+        if at < self.grad.numel():
+            keep.append((at, self.grad.numel()))
+        self._zero_pieces = keep
+        self._over_pieces = [(off, off + n) for off, n in sorted(ranges)]
+        self._covered = covered
+        self.narrow_zeroed = False
+
+    def zero_overwritten(self):
+        """The full fill after all: zero the overwritten ranges that the last
+        :meth:`zero_grad` left out."""
+        if self.narrow_zeroed:
+            for lo, hi in self._over_pieces:
+                self.grad[lo:hi].zero_()
+            self.narrow_zeroed = False
+
     def zero_grad(self):
-        self.grad.zero_()
+        if self._covered is not None and self._covered():
+            for lo, hi in self._zero_pieces:
+                self.grad[lo:hi].zero_()
+            self.narrow_zeroed = True
+        else:
+            self.grad.zero_()
+            self.narrow_zeroed = False
         if self.on_zero is not None:  # e.g. re-arm the fused engine's direct slots
             self.on_zero()
         # autograd may have replaced a view (e.g. after set_to_none); re-point

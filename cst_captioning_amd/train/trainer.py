@@ -130,6 +130,13 @@ class Trainer:
                 {k: self.bucket.grad[slot[id(p)][0]:slot[id(p)][0] + slot[id(p)][1]].view_as(p)
                  for k, p in named.items()}, named)
             self.bucket.on_zero = engine.arm_direct_slots
+            # zero_grad leaves the direct slots out of its fill when the engine
+            # reports that the coming backward overwrites all of them (the 84 MB
+            # fill shrinks to the few slices autograd accumulates into); a
+            # backward that takes another path zeroes them itself first
+            self.bucket.set_overwritten([slot[id(p)] for p in named.values()],
+                                        engine.direct_slots_covered)
+            engine.refill_direct_slots = self.bucket.zero_overwritten
         if getattr(opt, 'honor_optim_flags', 0):
             betas, eps = (opt.optim_alpha, opt.optim_beta), opt.optim_epsilon
         else:
@@ -167,11 +174,32 @@ class Trainer:
             self.scorer = build_scorer(self.opt, self.train_loader.ds, self.device)
         return self.scorer
 
+    def _feats(self, data):
+        """The batch's features for the model: where the fused FeatPool reads
+        them out of the HBM-resident tables by index, the tables + the batch's
+        index (no gathered copy in the step); else the gathered tensors."""
+        if self.engine is not None and hasattr(data, 'feats_indexed'):
+            f = data.feats_indexed()
+            if f is not None and self.engine.reads_by_index(self.model, f):
+                return f
+        return data['feats']
+
+    def _rollout_labels(self, data):
+        """The batch's labels for the engine's rollout: the resident label
+        table + the batch's caption rows (the decode kernels read the rows by
+        index, no gathered copy in the step); the gathered tensor where the
+        batch has no index form or already holds the copy."""
+        if self.engine is not None and hasattr(data, 'labels_indexed'):
+            lab = data.labels_indexed()
+            if lab is not None:
+                return lab
+        return data['labels']
+
     def _decode_rollout(self, data):
         """Forward pass.  Returns (sample_seq, sample_logprobs, pred)."""
         m = self.model
         if self.engine is not None:
-            return self.engine.rollout(m, data['feats'], data['labels'])
+            return self.engine.rollout(m, self._feats(data), self._rollout_labels(data))
         pred, seq, lp = m(data['feats'], data['labels'])
         return seq, lp, pred
 
@@ -182,11 +210,11 @@ class Trainer:
         vid = data['video_index']
         if opt.expand_feat == 1 and getattr(opt, 'dedupe_greedy', 1):
             with torch.no_grad():
-                g, _ = m.sample(data['feats'], {'sample_max': 1, 'expand_feat': 0})
+                g, _ = m.sample(self._feats(data), {'sample_max': 1, 'expand_feat': 0})
             gs = scorer.score(g, vid)
             return gs if per_video else gs.repeat_interleave(S)
         with torch.no_grad():
-            g, _ = m.sample(data['feats'], {'sample_max': 1, 'expand_feat': opt.expand_feat})
+            g, _ = m.sample(self._feats(data), {'sample_max': 1, 'expand_feat': opt.expand_feat})
         gvid = vid.repeat_interleave(S) if opt.expand_feat == 1 else vid
         return scorer.score(g, gvid)
 
@@ -212,7 +240,9 @@ class Trainer:
             # gathered HERE, on the main stream, before the event both decodes
             # order behind: gathered lazily by whichever decode touched it
             # first, the other stream would read it unordered
-            gathered = (data['feats'], data['labels'])  # (LazyGather: gathers now)
+            # (features the fused FeatPool reads by index, and labels the
+            # engine's rollout reads by index, have no gathered copy)
+            gathered = (self._feats(data), self._rollout_labels(data))  # (LazyGather: gathers now)
             del gathered
             stamps.mark('gathered')
             inputs_ready = self._ev_inputs
@@ -292,7 +322,7 @@ class Trainer:
 
     def xe_loss(self, data):
         if self.engine is not None:
-            lp = self.engine.teacher_forced(self.model, data['feats'], data['labels'])
+            lp = self.engine.teacher_forced(self.model, self._feats(data), data['labels'])
             self.timer.mark('rollout')
             # (a batch whose masks were not set by hand: the loader's caption
             # masks, derived from the labels)
