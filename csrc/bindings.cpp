@@ -2,6 +2,7 @@
 #include <torch/extension.h>
 
 #include "host/cider_host.h"
+#include "host/metric_host.h"
 #include "launchers.h"
 
 namespace cst {
@@ -98,6 +99,8 @@ double vocab_fwd_bench(at::Tensor hd, at::Tensor wlog, at::Tensor blog, at::Tens
                        int64_t flags, bool save, int64_t iters, int64_t variant);
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
                        double log_ref_len, int64_t use_eos);
+at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
+                        std::map<std::string, at::Tensor> t, int64_t use_eos);
 at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                           at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
                           double b1, double b2, double eps, double clip, double gscale,
@@ -165,6 +168,51 @@ static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
                    out.data_ptr<float>());
   return out;
 }
+
+// Sentence BLEU-4 / ROUGE-L: per-dataset tables (CPU tensors) and the native CPU
+// scorer; the host code's std::invalid_argument (over-limit inputs) surfaces as
+// ValueError.
+static std::map<std::string, at::Tensor> metric_build_tables(at::Tensor labels, at::Tensor start,
+                                                             at::Tensor end, int64_t use_eos) {
+  TORCH_CHECK(!labels.is_cuda() && labels.dim() == 2, "host builder takes a CPU (M, L) label table");
+  TORCH_CHECK(start.numel() == end.numel(), "one label range per video");
+  labels = labels.contiguous().to(at::kLong);
+  start = start.contiguous().to(at::kLong);
+  end = end.contiguous().to(at::kLong);
+  MetricTables t = build_metric_tables(labels.data_ptr<int64_t>(), (int)labels.size(0),
+                                       (int)labels.size(1), start.data_ptr<int64_t>(),
+                                       end.data_ptr<int64_t>(), (int)start.numel(), (int)use_eos);
+  return {{"vid_ref_off", to_tensor(t.vid_ref_off, at::kInt)},
+          {"ref_len", to_tensor(t.ref_len, at::kInt)},
+          {"vid_ng_off", to_tensor(t.vid_ng_off, at::kInt)},
+          {"ng_key", to_tensor(t.ng_key, at::kLong)},
+          {"ng_cnt", to_tensor(t.ng_cnt, at::kInt)},
+          {"ref_tok_off", to_tensor(t.ref_tok_off, at::kInt)},
+          {"ref_tok", to_tensor(t.ref_tok, at::kInt)}};
+}
+
+static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
+                                   at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
+                                   int64_t use_eos) {
+  const bool bleu = metric == "Bleu_4";
+  TORCH_CHECK(bleu || metric == "ROUGE_L", "metric_score_cpu: metric must be Bleu_4 or ROUGE_L, got ",
+              metric);
+  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
+                  hyp_video.size(0) == hyps.size(0),
+              "CPU hyps (N, T) and hyp_video (N)");
+  hyps = hyps.contiguous().to(at::kLong);
+  hyp_video = hyp_video.contiguous().to(at::kLong);
+  MetricTablesView v{(int)t.at("vid_ref_off").numel() - 1,
+                     t.at("vid_ref_off").data_ptr<int32_t>(), t.at("ref_len").data_ptr<int32_t>(),
+                     t.at("vid_ng_off").data_ptr<int32_t>(), t.at("ng_key").data_ptr<int64_t>(),
+                     t.at("ng_cnt").data_ptr<int32_t>(), t.at("ref_tok_off").data_ptr<int32_t>(),
+                     t.at("ref_tok").data_ptr<int32_t>()};
+  at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
+  (bleu ? bleu4_score_host : rouge_l_score_host)(
+      hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
+      hyp_video.data_ptr<int64_t>(), v, (int)use_eos, out.data_ptr<float>());
+  return out;
+}
 }  // namespace cst
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -183,6 +231,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("cider_build_tables", &cst::cider_build_tables);
   m.def("cider_score", &cst::cider_score);
   m.def("cider_score_cpu", &cst::cider_score_cpu);
+  m.def("metric_build_tables", &cst::metric_build_tables, py::arg("labels"), py::arg("start"),
+        py::arg("end"), py::arg("use_eos"),
+        "sentence BLEU-4 / ROUGE-L reference tables of a dataset (dict of CPU tensors)");
+  m.def("metric_score", &cst::metric_score, py::arg("metric"), py::arg("hyps"),
+        py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
+        "Bleu_4 | ROUGE_L sentence scores on the GPU (one launch, capturable)");
+  m.def("metric_score_cpu", &cst::metric_score_cpu, py::arg("metric"), py::arg("hyps"),
+        py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"));
   m.def("flat_adam_step", &cst::flat_adam_step);
   m.def("refresh_shadows", &cst::refresh_shadows);
   m.def("vocab_fwd_bench", &cst::vocab_fwd_bench);

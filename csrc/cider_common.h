@@ -40,4 +40,29 @@ CST_HD float df_lookup(const int64_t* keys, const float* vals, uint32_t cap, uin
   return 0.f;
 }
 
+#if defined(__HIPCC__)
+// Hypothesis compaction shared by the reward kernels (cider_d.hip,
+// sent_metrics.hip), run by ONE whole wavefront on row `row` of (., T <= 64)
+// tokens: reproduces array_to_str -- drop BOS (=1) anywhere, stop at the first
+// EOS (=0) and keep that 0 when use_eos.  Writes the W kept tokens to
+// s_tok[0..W) (64 ints, LDS) and returns W (<= 64), the same in every lane.
+// The caller orders the LDS writes before other lanes' reads.
+__device__ __forceinline__ int compact_hypothesis(const int64_t* __restrict__ row, int T, int lane,
+                                                  int use_eos, int* s_tok) {
+  const int tok = lane < T ? (int)row[lane] : 0;
+  const uint64_t zmask = __ballot(lane >= T || tok == 0);
+  const int e = zmask ? __ffsll((long long)zmask) - 1 : 64;  // first EOS (or end)
+  const bool keep = lane < e && tok != 1;
+  const uint64_t kmask = __ballot(keep);
+  const int pos = __popcll(kmask & ((1ull << lane) - 1ull));
+  int W = __popcll(kmask);
+  if (keep) s_tok[pos] = tok;
+  if (use_eos && e < T) {
+    if (lane == 0) s_tok[W] = 0;
+    W += 1;
+  }
+  return W;
+}
+#endif
+
 }  // namespace cst

@@ -2077,6 +2077,47 @@ at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::stri
   return out;
 }
 
+// On-GPU sentence BLEU-4 / ROUGE-L scores of N hypotheses (kernels/sent_metrics.hip).
+// No allocation besides the result and no synchronisation: capturable.
+at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
+                        std::map<std::string, at::Tensor> t, int64_t use_eos) {
+  check_cuda(hyps, "hyps");
+  check_cuda(hyp_video, "hyp_video");
+  TORCH_CHECK(hyps.dim() == 2 && hyp_video.dim() == 1 && hyp_video.size(0) == hyps.size(0),
+              "hyps (N, T) and hyp_video (N)");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
+              "int64 inputs");
+  const bool bleu = metric == "Bleu_4";
+  TORCH_CHECK(bleu || metric == "ROUGE_L", "metric_score: metric must be Bleu_4 or ROUGE_L, got ",
+              metric);
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  TORCH_CHECK(T <= 64, "hypotheses of ", T, " tokens; at most 64 are supported");
+  for (const char* k : {"vid_ref_off", "ref_len", "vid_ng_off", "ng_key", "ng_cnt", "ref_tok_off",
+                        "ref_tok"}) {
+    TORCH_CHECK(t.count(k), "metric tables lack ", k);
+    check_cuda(t[k], k);
+    TORCH_CHECK(t[k].scalar_type() == (std::string(k) == "ng_key" ? at::kLong : at::kInt),
+                "metric table ", k, " has the wrong dtype");
+  }
+  const int Nv = (int)t["vid_ref_off"].numel() - 1;
+  TORCH_CHECK(Nv >= 0 && t["vid_ng_off"].numel() == Nv + 1 &&
+                  t["ref_tok_off"].numel() == t["ref_len"].numel() + 1,
+              "metric tables are inconsistent");
+  at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
+  if (bleu)
+    launch_bleu4(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                 t["vid_ref_off"].data_ptr<int32_t>(), t["ref_len"].data_ptr<int32_t>(),
+                 t["vid_ng_off"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
+                 t["ng_cnt"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
+                 cur_stream());
+  else
+    launch_rouge_l(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                   t["vid_ref_off"].data_ptr<int32_t>(), t["ref_tok_off"].data_ptr<int32_t>(),
+                   t["ref_tok"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
+                   cur_stream());
+  return out;
+}
+
 // Shadow-copy segments from Python: meta = int64 CPU (n, 8) rows {off, n,
 // kind, cols, H, E, ld2, slots}; dsts = 2 tensors per row (dst, dst2; undefined or
 // empty when unused).

@@ -1,0 +1,177 @@
+// Native host side of the sentence-level BLEU-4 / ROUGE-L rewards (no torch
+// dependency).
+//
+//  * build_metric_tables: once per dataset, reduces every GT label row as
+//    utils/text.py::sequence_tokens does (BOS dropped anywhere, stop at the
+//    first EOS, that 0 kept when use_eos) and builds, per video, the sorted
+//    union of the references' packed n-grams with their clip counts (BLEU) and
+//    the ragged reference token rows (ROUGE).
+//  * bleu4_score_host / rouge_l_score_host: the scorers of eval/metrics.py
+//    (Bleu per-sentence scores, Rouge.calc_score) on those tables, integer
+//    counts and fp64 formulas rounded once to fp32.  They are the
+//    backend='cpu' scorer and a second oracle of the GPU kernels
+//    (csrc/kernels/sent_metrics.hip).
+#include "metric_host.h"
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <stdexcept>
+#include <string>
+
+#include "../cider_common.h"
+
+namespace cst {
+
+static void reduce_tokens(const int64_t* row, int T, int use_eos, bool check_pack,
+                          const char* what, std::vector<int>& out) {
+  out.clear();
+  for (int i = 0; i < T; ++i) {
+    const int64_t t = row[i];
+    if (t == 0) {
+      if (use_eos) out.push_back(0);
+      return;
+    }
+    if (t == 1) continue;
+    if (t < 0 || (check_pack && t > METRIC_MAX_TOKEN))
+      throw std::invalid_argument(std::string(what) + " token id " + std::to_string(t) +
+                                  " outside [0, 65534]: the packed n-gram keys hold 16 bits "
+                                  "per token");
+    out.push_back((int)t);
+  }
+}
+
+static void count_ngrams(const std::vector<int>& toks, std::map<uint64_t, int>& cnt) {
+  cnt.clear();
+  const int W = (int)toks.size();
+  for (int n = 1; n <= 4; ++n)
+    for (int i = 0; i + n <= W; ++i) {
+      uint64_t key = 0;
+      for (int j = 0; j < n; ++j) key |= (uint64_t)(toks[i + j] + 1) << (16 * j);
+      cnt[key] += 1;
+    }
+}
+
+MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int64_t* start,
+                                 const int64_t* end, int Nv, int use_eos) {
+  MetricTables t;
+  t.vid_ref_off.resize(Nv + 1);
+  t.vid_ng_off.resize(Nv + 1);
+  t.ref_tok_off.push_back(0);
+  std::vector<int> toks;
+  std::map<uint64_t, int> grams, maxc;
+  int nref = 0;
+  for (int v = 0; v < Nv; ++v) {
+    t.vid_ref_off[v] = nref;
+    t.vid_ng_off[v] = (int32_t)t.ng_key.size();
+    if (start[v] < 0 || end[v] > M)
+      throw std::invalid_argument("label range of video " + std::to_string(v) +
+                                  " lies outside the label table");
+    maxc.clear();
+    for (int64_t r = start[v]; r < end[v]; ++r) {
+      reduce_tokens(labels + r * L, L, use_eos, true, "reference", toks);
+      if ((int)toks.size() > METRIC_MAXT)
+        throw std::invalid_argument("reference " + std::to_string(r) + " has " +
+                                    std::to_string(toks.size()) + " tokens; at most 64 are "
+                                    "supported");
+      count_ngrams(toks, grams);
+      for (auto& g : grams) {
+        int& m = maxc[g.first];
+        m = std::max(m, g.second);
+      }
+      t.ref_len.push_back((int32_t)toks.size());
+      t.ref_tok.insert(t.ref_tok.end(), toks.begin(), toks.end());
+      t.ref_tok_off.push_back((int32_t)t.ref_tok.size());
+      ++nref;
+    }
+    for (auto& g : maxc) {  // (std::map: ascending keys)
+      t.ng_key.push_back((int64_t)g.first);
+      t.ng_cnt.push_back(g.second);
+    }
+  }
+  t.vid_ref_off[Nv] = nref;
+  t.vid_ng_off[Nv] = (int32_t)t.ng_key.size();
+  return t;
+}
+
+static void check_hyps(int T, const int64_t* hyp_video, int N, int Nv) {
+  if (T > METRIC_MAXT)
+    throw std::invalid_argument("hypotheses of " + std::to_string(T) +
+                                " tokens; at most 64 are supported");
+  for (int i = 0; i < N; ++i)
+    if (hyp_video[i] < 0 || hyp_video[i] >= Nv)
+      throw std::invalid_argument("video index " + std::to_string(hyp_video[i]) +
+                                  " outside the tables");
+}
+
+void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                      const MetricTablesView& t, int use_eos, float* out) {
+  check_hyps(T, hyp_video, N, t.Nv);
+  const double tiny = 1e-15, small = 1e-9;
+  std::vector<int> toks;
+  std::map<uint64_t, int> grams;
+  for (int i = 0; i < N; ++i) {
+    reduce_tokens(hyps + (int64_t)i * T, T, use_eos, true, "hypothesis", toks);
+    const int v = (int)hyp_video[i];
+    const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
+    if (r1 <= r0) {
+      out[i] = 0.f;
+      continue;
+    }
+    count_ngrams(toks, grams);
+    const int64_t* k0 = t.ng_key + t.vid_ng_off[v];
+    const int64_t* k1 = t.ng_key + t.vid_ng_off[v + 1];
+    int correct[4] = {0, 0, 0, 0};
+    for (auto& g : grams) {
+      // (ascending as uint64: a 4-gram whose last token is >= 32767 has bit 63 set)
+      const int64_t* p = std::lower_bound(
+          k0, k1, (int64_t)g.first,
+          [](int64_t a, int64_t b) { return (uint64_t)a < (uint64_t)b; });
+      if (p != k1 && *p == (int64_t)g.first)
+        correct[ngram_order(g.first) - 1] += std::min(g.second, t.ng_cnt[p - t.ng_key]);
+    }
+    const int tlen = (int)toks.size();
+    // closest reference length, ties to the shorter: min over (|len_r - tlen|, len_r)
+    int best_d = 1 << 30, rlen = 0;
+    for (int r = r0; r < r1; ++r) {
+      const int d = std::abs(t.ref_len[r] - tlen);
+      if (d < best_d || (d == best_d && t.ref_len[r] < rlen)) best_d = d, rlen = t.ref_len[r];
+    }
+    double b = 1.0;
+    for (int k = 0; k < 4; ++k) b *= (correct[k] + tiny) / (std::max(0, tlen - k) + small);
+    double s = std::pow(b, 0.25);
+    const double ratio = (tlen + tiny) / (rlen + small);
+    if (ratio < 1) s *= std::exp(1 - 1 / ratio);
+    out[i] = (float)s;
+  }
+}
+
+void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                        const MetricTablesView& t, int use_eos, float* out) {
+  check_hyps(T, hyp_video, N, t.Nv);
+  const double beta = 1.2, b2 = beta * beta;
+  std::vector<int> toks, prev, cur;
+  for (int i = 0; i < N; ++i) {
+    reduce_tokens(hyps + (int64_t)i * T, T, use_eos, false, "hypothesis", toks);
+    const int v = (int)hyp_video[i];
+    const int W = (int)toks.size();
+    double p = 0, rc = 0;
+    for (int r = t.vid_ref_off[v]; r < t.vid_ref_off[v + 1]; ++r) {
+      const int32_t* ref = t.ref_tok + t.ref_tok_off[r];
+      const int n = t.ref_tok_off[r + 1] - t.ref_tok_off[r];
+      prev.assign(W + 1, 0);
+      for (int a = 0; a < n; ++a) {
+        cur.assign(W + 1, 0);
+        for (int j = 0; j < W; ++j)
+          cur[j + 1] = ref[a] == toks[j] ? prev[j] + 1 : std::max(prev[j + 1], cur[j]);
+        prev.swap(cur);
+      }
+      const int l = prev[W];
+      if (W > 0) p = std::max(p, l / (double)W);
+      if (n > 0) rc = std::max(rc, l / (double)n);
+    }
+    out[i] = (p != 0 && rc != 0) ? (float)(((1 + b2) * p * rc) / (rc + b2 * p)) : 0.f;
+  }
+}
+
+}  // namespace cst

@@ -1,0 +1,57 @@
+// Sentence-level BLEU-4 / ROUGE-L rewards: per-dataset reference tables and
+// the native CPU scorers (see metric_host.cpp).
+#pragma once
+#include <stdint.h>
+
+#include <vector>
+
+namespace cst {
+
+constexpr int METRIC_MAXT = 64;            // hypothesis width and reference length limit
+constexpr int64_t METRIC_MAX_TOKEN = 65534;  // BLEU: token + 1 must fit the 16-bit packing
+
+struct MetricTables {
+  std::vector<int32_t> vid_ref_off;  // (Nv + 1) references of video v: [off[v], off[v+1])
+  std::vector<int32_t> ref_len;      // (nref) reduced length of every reference
+  // BLEU: per video the union of its references' n-grams (n <= 4) as packed
+  // keys in ascending order (which groups them by order), each with the
+  // maximum count over the references (the clip count)
+  std::vector<int32_t> vid_ng_off;   // (Nv + 1)
+  std::vector<int64_t> ng_key;
+  std::vector<int32_t> ng_cnt;
+  // ROUGE: the reduced reference token rows, ragged
+  std::vector<int32_t> ref_tok_off;  // (nref + 1)
+  std::vector<int32_t> ref_tok;
+};
+
+struct MetricTablesView {
+  int Nv;
+  const int32_t* vid_ref_off;
+  const int32_t* ref_len;
+  const int32_t* vid_ng_off;
+  const int64_t* ng_key;
+  const int32_t* ng_cnt;
+  const int32_t* ref_tok_off;
+  const int32_t* ref_tok;
+};
+
+inline MetricTablesView view_of(const MetricTables& t) {
+  return {(int)t.vid_ref_off.size() - 1, t.vid_ref_off.data(), t.ref_len.data(),
+          t.vid_ng_off.data(),           t.ng_key.data(),      t.ng_cnt.data(),
+          t.ref_tok_off.data(),          t.ref_tok.data()};
+}
+
+// Throws std::invalid_argument when a reference is longer than METRIC_MAXT
+// tokens or holds a token outside [0, METRIC_MAX_TOKEN].
+MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int64_t* start,
+                                 const int64_t* end, int Nv, int use_eos);
+
+// (N, T) hypotheses, T <= METRIC_MAXT (std::invalid_argument otherwise; BLEU
+// also rejects tokens above METRIC_MAX_TOKEN).  A video without references
+// scores 0.
+void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                      const MetricTablesView& t, int use_eos, float* out);
+void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                        const MetricTablesView& t, int use_eos, float* out);
+
+}  // namespace cst

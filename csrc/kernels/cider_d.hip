@@ -49,18 +49,7 @@ __global__ __launch_bounds__(256) void cider_d_kernel(
 
   // -- 1. compaction (wave 0) ----------------------------------------------------
   if (w == 0) {
-    const int tok = lane < T ? (int)hyps[(int64_t)hyp * T + lane] : 0;
-    const uint64_t zmask = __ballot(lane >= T || tok == 0);
-    const int e = zmask ? __ffsll((long long)zmask) - 1 : 64;  // first EOS (or end)
-    const bool keep = lane < e && tok != 1;
-    const uint64_t kmask = __ballot(keep);
-    const int pos = __popcll(kmask & ((1ull << lane) - 1ull));
-    int W = __popcll(kmask);
-    if (keep) s_tok[pos] = tok;
-    if (use_eos && e < T) {
-      if (lane == 0) s_tok[W] = 0;
-      W += 1;
-    }
+    const int W = compact_hypothesis(hyps + (int64_t)hyp * T, T, lane, use_eos, s_tok);
     if (lane == 0) s_W = W;
   }
   __syncthreads();

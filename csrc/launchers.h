@@ -62,6 +62,16 @@ void launch_cider_d(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
                     const float* ng_val, float log_ref_len, int use_eos, float* out,
                     hipStream_t stream);
 
+// sent_metrics.hip: sentence BLEU-4 / ROUGE-L of N hypotheses (T <= 64), one
+// wavefront each, against the tables of host/metric_host.h (Nv videos)
+void launch_bleu4(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
+                  const int32_t* vid_ref_off, const int32_t* ref_len, const int32_t* vid_ng_off,
+                  const int64_t* ng_key, const int32_t* ng_cnt, int use_eos, float* out,
+                  hipStream_t stream);
+void launch_rouge_l(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
+                    const int32_t* vid_ref_off, const int32_t* ref_tok_off,
+                    const int32_t* ref_tok, int use_eos, float* out, hipStream_t stream);
+
 // adam.hip
 // bf16 shadow copies of decoder weights written by the optimizer pass
 // (GATES kinds: a recurrent cell's W_ih / W_hh, rows scattered into the packed

@@ -104,8 +104,9 @@ class CiderDScorer:
 
 
 class GenericScorer:
-    """Any reference-style scorer (Bleu_4 / METEOR / ROUGE_L) on the CPU,
-    for ``--eval_metric`` values other than CIDEr (``train.py:119-124``)."""
+    """Any reference-style scorer on the CPU (``train.py:119-124``): METEOR,
+    which needs the stemmer; Bleu_4 / ROUGE_L have kernels
+    (:mod:`.sent_metrics`) and come here only to be timed against them."""
 
     def __init__(self, dataset, scorer, use_eos=0):
         self.ds, self.scorer, self.use_eos = dataset, scorer, int(use_eos)

@@ -40,7 +40,13 @@ def score_hypotheses(scorer, hyps, gts, seq_per_img, expand_feat=1, use_eos=0,
     n = hyps.shape[0]
     n_rows = n if n_rows is None else n_rows
     refs = [[array_to_str(r, use_eos) for r in g] for g in gts]
-    res = [{'image_id': i, 'caption': [array_to_str(hyps[i], use_eos)]} for i in range(n)]
+    from ..eval.metrics import Bleu, Meteor, Rouge  # (imports this package: not at the top)
+    if isinstance(scorer, (Bleu, Meteor, Rouge)):
+        # the coco-style scorers index res[key][0]: the reference hands the
+        # list form to CiderD only (utils.py:194-198)
+        res = {i: [array_to_str(hyps[i], use_eos)] for i in range(n)}
+    else:
+        res = [{'image_id': i, 'caption': [array_to_str(hyps[i], use_eos)]} for i in range(n)]
     gts_map = {i: refs[_hyp_video(i, n_rows, seq_per_img, expand_feat)] for i in range(n)}
     if hasattr(scorer, 'compute_score_tokens'):
         return np.asarray(scorer.compute_score_tokens(gts_map, res), dtype=np.float64)

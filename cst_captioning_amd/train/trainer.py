@@ -64,14 +64,19 @@ def maybe_inject_fault(rank, it):
 
 def build_scorer(opt, dataset, device):
     metric = opt.eval_metric
+    backend = 'auto'
+    if getattr(opt, 'reward_device', 'gpu') == 'cpu':
+        backend = 'cpu-ref'
     if metric in ('CIDEr', 'MSRVTT', 'Loss'):
-        backend = 'auto'
-        if getattr(opt, 'reward_device', 'gpu') == 'cpu':
-            backend = 'cpu-ref'
         return CiderDScorer(dataset, use_eos=opt.use_eos, device=device, backend=backend)
-    from ..eval.metrics import Bleu, Meteor, Rouge
-    sc = {'Bleu_4': Bleu(4), 'METEOR': Meteor(), 'ROUGE_L': Rouge()}[metric]
-    return GenericScorer(dataset, sc, opt.use_eos)
+    if metric in ('Bleu_4', 'ROUGE_L'):
+        from ..ops.sent_metrics import SentenceMetricScorer
+        return SentenceMetricScorer(dataset, metric, use_eos=opt.use_eos, device=device,
+                                    backend=backend)
+    from ..eval.metrics import Meteor
+    if metric != 'METEOR':
+        raise ValueError('no reward scorer for --eval_metric %r' % (metric,))
+    return GenericScorer(dataset, Meteor(), opt.use_eos)  # (needs the stemmer: CPU only)
 
 
 class Trainer:
@@ -473,8 +478,13 @@ class Trainer:
     # Under data parallelism the gradient all-reduce stays an eager RCCL call
     # between two graphs (forward/backward, then update).
     def _graph_enabled(self):
-        return (self.engine is not None and self.device.type == 'cuda'
-                and bool(getattr(self.opt, 'cuda_graph', 1)) and not self.timer.enabled)
+        if not (self.engine is not None and self.device.type == 'cuda'
+                and bool(getattr(self.opt, 'cuda_graph', 1)) and not self.timer.enabled):
+            return False
+        # an RL step whose reward is scored on the host (METEOR,
+        # --reward_device cpu) copies the samples back inside the step: it
+        # cannot be captured and runs eagerly
+        return not self.rl_training or self._ensure_scorer().backend == 'gpu'
 
     def _graph_signature(self, idx, mixer_from, scb):
         return (self.rl_training, mixer_from, scb, float(self.model.ss_prob),

@@ -6,7 +6,8 @@ Produces ``cst_captioning_amd/_C*.so`` from ``csrc/``:
     ``hipcc --offload-arch=gfx950`` (no hipify pass: torch's CUDAExtension
     would rewrite the sources into *_hip copies, so it is not used);
   * ``csrc/*.cpp``, ``csrc/host/*.cpp`` -- the C++ host runtime (decoder
-    executor, CIDEr-D table builder / CPU scorer, bindings), compiled as a
+    executor, CIDEr-D and BLEU-4 / ROUGE-L table builders / CPU scorers,
+    bindings), compiled as a
     regular torch C++ extension against the ROCm headers and linked with the
     HIP objects and ``libamdhip64``.
 """
@@ -79,7 +80,7 @@ SANITIZE = os.environ.get('CSTCAP_HOST_SANITIZE') == '1'
 ext = CppExtension(
     'cst_captioning_amd._C_san' if SANITIZE else 'cst_captioning_amd._C',
     ['csrc/engine.cpp', 'csrc/bindings.cpp', 'csrc/host/cider_host.cpp',
-     'csrc/host/blaslt_tuned.cpp'],
+     'csrc/host/metric_host.cpp', 'csrc/host/blaslt_tuned.cpp'],
     include_dirs=[os.path.join(HERE, 'csrc')] + include_paths(device_type='cuda'),
     define_macros=[('__HIP_PLATFORM_AMD__', '1'), ('USE_ROCM', '1')]
     + ([('_GLIBCXX_ASSERTIONS', '1')] if SANITIZE else []),
