@@ -98,7 +98,10 @@ std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor 
 double vocab_fwd_bench(at::Tensor hd, at::Tensor wlog, at::Tensor blog, at::Tensor tgt,
                        int64_t flags, bool save, int64_t iters, int64_t variant);
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                       double log_ref_len, int64_t use_eos);
+                       double log_ref_len, int64_t use_eos, bool clipped);
+at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t);
+std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
+                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids);
 at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
                         std::map<std::string, at::Tensor> t, int64_t use_eos);
 at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
@@ -154,7 +157,7 @@ static std::map<std::string, at::Tensor> cider_build_tables(at::Tensor labels, a
 
 static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                   std::map<std::string, at::Tensor> t, double log_ref_len,
-                                  int64_t use_eos) {
+                                  int64_t use_eos, bool clipped) {
   hyps = hyps.contiguous().to(at::kLong);
   hyp_video = hyp_video.contiguous().to(at::kLong);
   CiderTablesView v{(uint32_t)t["ht_keys"].numel(), t["ht_keys"].data_ptr<int64_t>(),
@@ -165,30 +168,42 @@ static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
   at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
   cider_score_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
                    hyp_video.data_ptr<int64_t>(), v, log_ref_len, (int)use_eos,
-                   out.data_ptr<float>());
+                   out.data_ptr<float>(), clipped);
   return out;
 }
 
 // Sentence BLEU-4 / ROUGE-L: per-dataset tables (CPU tensors) and the native CPU
 // scorer; the host code's std::invalid_argument (over-limit inputs) surfaces as
 // ValueError.
-static std::map<std::string, at::Tensor> metric_build_tables(at::Tensor labels, at::Tensor start,
-                                                             at::Tensor end, int64_t use_eos) {
+static std::map<std::string, at::Tensor> metric_build_tables(
+    at::Tensor labels, at::Tensor start, at::Tensor end, int64_t use_eos,
+    c10::optional<at::Tensor> stem_ids) {
   TORCH_CHECK(!labels.is_cuda() && labels.dim() == 2, "host builder takes a CPU (M, L) label table");
   TORCH_CHECK(start.numel() == end.numel(), "one label range per video");
   labels = labels.contiguous().to(at::kLong);
   start = start.contiguous().to(at::kLong);
   end = end.contiguous().to(at::kLong);
-  MetricTables t = build_metric_tables(labels.data_ptr<int64_t>(), (int)labels.size(0),
-                                       (int)labels.size(1), start.data_ptr<int64_t>(),
-                                       end.data_ptr<int64_t>(), (int)start.numel(), (int)use_eos);
-  return {{"vid_ref_off", to_tensor(t.vid_ref_off, at::kInt)},
-          {"ref_len", to_tensor(t.ref_len, at::kInt)},
-          {"vid_ng_off", to_tensor(t.vid_ng_off, at::kInt)},
-          {"ng_key", to_tensor(t.ng_key, at::kLong)},
-          {"ng_cnt", to_tensor(t.ng_cnt, at::kInt)},
-          {"ref_tok_off", to_tensor(t.ref_tok_off, at::kInt)},
-          {"ref_tok", to_tensor(t.ref_tok, at::kInt)}};
+  at::Tensor stems;
+  if (stem_ids.has_value()) {
+    TORCH_CHECK(!stem_ids->is_cuda() && stem_ids->dim() == 1, "stem_ids: CPU (V)");
+    stems = stem_ids->contiguous().to(at::kInt);
+  }
+  MetricTables t = build_metric_tables(
+      labels.data_ptr<int64_t>(), (int)labels.size(0), (int)labels.size(1),
+      start.data_ptr<int64_t>(), end.data_ptr<int64_t>(), (int)start.numel(), (int)use_eos,
+      stems.defined() ? stems.data_ptr<int32_t>() : nullptr,
+      stems.defined() ? (int)stems.numel() : 0);
+  std::map<std::string, at::Tensor> out = {
+      {"vid_ref_off", to_tensor(t.vid_ref_off, at::kInt)},
+      {"ref_len", to_tensor(t.ref_len, at::kInt)},
+      {"vid_ng_off", to_tensor(t.vid_ng_off, at::kInt)},
+      {"ng_key", to_tensor(t.ng_key, at::kLong)},
+      {"ng_cnt", to_tensor(t.ng_cnt, at::kInt)},
+      {"ref_tok_off", to_tensor(t.ref_tok_off, at::kInt)},
+      {"ref_tok", to_tensor(t.ref_tok, at::kInt)}};
+  if (stems.defined())  // (validation scorer: the references' stem rows as well)
+    out["ref_stem"] = to_tensor(t.ref_stem, at::kInt);
+  return out;
 }
 
 static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
@@ -213,6 +228,48 @@ static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
       hyp_video.data_ptr<int64_t>(), v, (int)use_eos, out.data_ptr<float>());
   return out;
 }
+
+// Validation scorer on the CPU: the host twins of kernels/corpus_metrics.hip.
+static MetricTablesView metric_view(std::map<std::string, at::Tensor>& t) {
+  return {(int)t.at("vid_ref_off").numel() - 1,
+          t.at("vid_ref_off").data_ptr<int32_t>(), t.at("ref_len").data_ptr<int32_t>(),
+          t.at("vid_ng_off").data_ptr<int32_t>(), t.at("ng_key").data_ptr<int64_t>(),
+          t.at("ng_cnt").data_ptr<int32_t>(), t.at("ref_tok_off").data_ptr<int32_t>(),
+          t.at("ref_tok").data_ptr<int32_t>()};
+}
+
+static at::Tensor bleu_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
+                                 std::map<std::string, at::Tensor> t) {
+  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
+                  hyp_video.size(0) == hyps.size(0),
+              "CPU hyps (N, T) and hyp_video (N)");
+  hyps = hyps.contiguous().to(at::kLong);
+  hyp_video = hyp_video.contiguous().to(at::kLong);
+  at::Tensor out = at::empty({hyps.size(0), 10}, at::TensorOptions().dtype(at::kInt));
+  bleu_stats_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
+                  hyp_video.data_ptr<int64_t>(), metric_view(t), out.data_ptr<int32_t>());
+  return out;
+}
+
+static std::vector<at::Tensor> meteor_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
+                                                std::map<std::string, at::Tensor> t,
+                                                at::Tensor stem_ids) {
+  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
+                  hyp_video.size(0) == hyps.size(0),
+              "CPU hyps (N, T) and hyp_video (N)");
+  TORCH_CHECK(t.count("ref_stem") && t.at("ref_stem").numel() == t.at("ref_tok").numel(),
+              "metric tables were built without stem ids");
+  hyps = hyps.contiguous().to(at::kLong);
+  hyp_video = hyp_video.contiguous().to(at::kLong);
+  stem_ids = stem_ids.contiguous().to(at::kInt);
+  at::Tensor stats = at::empty({hyps.size(0), 6}, at::TensorOptions().dtype(at::kInt));
+  at::Tensor score = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kDouble));
+  meteor_stats_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
+                    hyp_video.data_ptr<int64_t>(), metric_view(t),
+                    t.at("ref_stem").data_ptr<int32_t>(), stem_ids.data_ptr<int32_t>(),
+                    (int)stem_ids.numel(), stats.data_ptr<int32_t>(), score.data_ptr<double>());
+  return {stats, score};
+}
 }  // namespace cst
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -229,11 +286,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("exp_zero_off") = false, py::arg("dw_slots") = std::vector<at::Tensor>(),
         py::arg("vg_idx") = py::none(), py::arg("vg_C") = 1);
   m.def("cider_build_tables", &cst::cider_build_tables);
-  m.def("cider_score", &cst::cider_score);
-  m.def("cider_score_cpu", &cst::cider_score_cpu);
+  // clipped = false: coco CIDEr (no clipping, no length penalty), the validation metric
+  m.def("cider_score", &cst::cider_score, py::arg("hyps"), py::arg("hyp_video"),
+        py::arg("tables"), py::arg("log_ref_len"), py::arg("use_eos"),
+        py::arg("clipped") = true);
+  m.def("cider_score_cpu", &cst::cider_score_cpu, py::arg("hyps"), py::arg("hyp_video"),
+        py::arg("tables"), py::arg("log_ref_len"), py::arg("use_eos"),
+        py::arg("clipped") = true);
   m.def("metric_build_tables", &cst::metric_build_tables, py::arg("labels"), py::arg("start"),
-        py::arg("end"), py::arg("use_eos"),
-        "sentence BLEU-4 / ROUGE-L reference tables of a dataset (dict of CPU tensors)");
+        py::arg("end"), py::arg("use_eos"), py::arg("stem_ids") = py::none(),
+        "sentence BLEU-4 / ROUGE-L reference tables of a dataset (dict of CPU tensors); with "
+        "stem_ids (V) also the references' stem rows (METEOR)");
+  m.def("bleu_stats", &cst::bleu_stats, py::arg("hyps"), py::arg("hyp_video"), py::arg("tables"),
+        "corpus BLEU statistics per hypothesis on the GPU: (N, 10) int32");
+  m.def("bleu_stats_cpu", &cst::bleu_stats_cpu, py::arg("hyps"), py::arg("hyp_video"),
+        py::arg("tables"));
+  m.def("meteor_stats", &cst::meteor_stats, py::arg("hyps"), py::arg("hyp_video"),
+        py::arg("tables"), py::arg("stem_ids"),
+        "METEOR alignment statistics per hypothesis on the GPU: (N, 6) int32, (N) fp64");
+  m.def("meteor_stats_cpu", &cst::meteor_stats_cpu, py::arg("hyps"), py::arg("hyp_video"),
+        py::arg("tables"), py::arg("stem_ids"));
   m.def("metric_score", &cst::metric_score, py::arg("metric"), py::arg("hyps"),
         py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
         "Bleu_4 | ROUGE_L sentence scores on the GPU (one launch, capturable)");

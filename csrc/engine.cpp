@@ -2059,15 +2059,18 @@ at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, in
 
 // On-GPU CIDEr-D scores of N hypotheses.
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                       double log_ref_len, int64_t use_eos) {
+                       double log_ref_len, int64_t use_eos, bool clipped) {
   check_cuda(hyps, "hyps");
   check_cuda(hyp_video, "hyp_video");
   TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
               "int64 inputs");
   const int64_t N = hyps.size(0), T = hyps.size(1);
-  TORCH_CHECK(T <= 63, "hypotheses longer than 63 tokens are not supported");
+  // (clipped = false: coco CIDEr of the validation scorer, up to 64 tokens)
+  TORCH_CHECK(T <= (clipped ? 63 : 64), "hypotheses longer than ", clipped ? 63 : 64,
+              " tokens are not supported");
   at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
-  launch_cider_d(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N,
+  (clipped ? launch_cider_d : launch_cider_unclipped)(
+      hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N,
                  t["ht_keys"].data_ptr<int64_t>(), t["ht_vals"].data_ptr<float>(),
                  (uint32_t)t["ht_keys"].numel(), t["vid_ref_off"].data_ptr<int32_t>(),
                  t["ref_ng_off"].data_ptr<int32_t>(), t["ref_norm"].data_ptr<float>(),
@@ -2116,6 +2119,71 @@ at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor h
                    t["ref_tok"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
                    cur_stream());
   return out;
+}
+
+// Validation scorer (kernels/corpus_metrics.hip): per-hypothesis statistics of
+// corpus BLEU ((N, 10) int32) or METEOR ((N, 6) int32 and the (N) fp64 segment
+// scores) against the tables of metric_build_tables (METEOR: built with stem
+// ids, which are passed again for the hypothesis tokens).
+static int check_corpus_inputs(at::Tensor& hyps, at::Tensor& hyp_video,
+                               std::map<std::string, at::Tensor>& t,
+                               std::initializer_list<const char*> keys) {
+  check_cuda(hyps, "hyps");
+  check_cuda(hyp_video, "hyp_video");
+  TORCH_CHECK(hyps.dim() == 2 && hyp_video.dim() == 1 && hyp_video.size(0) == hyps.size(0),
+              "hyps (N, T) and hyp_video (N)");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong &&
+                  hyps.is_contiguous() && hyp_video.is_contiguous(),
+              "contiguous int64 inputs");
+  TORCH_CHECK(hyps.size(1) <= 64, "hypotheses of ", hyps.size(1),
+              " tokens; at most 64 are supported");
+  for (const char* k : keys) {
+    TORCH_CHECK(t.count(k), "metric tables lack ", k);
+    check_cuda(t[k], k);
+    TORCH_CHECK(t[k].scalar_type() == (std::string(k) == "ng_key" ? at::kLong : at::kInt) &&
+                    t[k].is_contiguous(),
+                "metric table ", k, " has the wrong dtype or layout");
+  }
+  const int Nv = (int)t["vid_ref_off"].numel() - 1;
+  TORCH_CHECK(Nv >= 0, "metric tables are inconsistent");
+  return Nv;
+}
+
+at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t) {
+  const int Nv = check_corpus_inputs(hyps, hyp_video, t,
+                                     {"vid_ref_off", "ref_len", "vid_ng_off", "ng_key", "ng_cnt"});
+  TORCH_CHECK(t["vid_ng_off"].numel() == Nv + 1 && t["ng_cnt"].numel() == t["ng_key"].numel(),
+              "metric tables are inconsistent");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  at::Tensor out = at::empty({N, 10}, hyps.options().dtype(at::kInt));
+  launch_bleu_stats(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                    t["vid_ref_off"].data_ptr<int32_t>(), t["ref_len"].data_ptr<int32_t>(),
+                    t["vid_ng_off"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
+                    t["ng_cnt"].data_ptr<int32_t>(), out.data_ptr<int32_t>(), cur_stream());
+  return out;
+}
+
+std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
+                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids) {
+  const int Nv = check_corpus_inputs(hyps, hyp_video, t,
+                                     {"vid_ref_off", "ref_len", "ref_tok_off", "ref_tok",
+                                      "ref_stem"});
+  check_cuda(stem_ids, "stem_ids");
+  TORCH_CHECK(stem_ids.scalar_type() == at::kInt && stem_ids.dim() == 1 &&
+                  stem_ids.is_contiguous(),
+              "stem_ids: contiguous int32 (V)");
+  TORCH_CHECK(t["ref_tok_off"].numel() == t["ref_len"].numel() + 1 &&
+                  t["ref_stem"].numel() == t["ref_tok"].numel(),
+              "metric tables are inconsistent (built without stem ids?)");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  at::Tensor stats = at::empty({N, 6}, hyps.options().dtype(at::kInt));
+  at::Tensor score = at::empty({N}, hyps.options().dtype(at::kDouble));
+  launch_meteor_stats(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                      t["vid_ref_off"].data_ptr<int32_t>(), t["ref_tok_off"].data_ptr<int32_t>(),
+                      t["ref_tok"].data_ptr<int32_t>(), t["ref_stem"].data_ptr<int32_t>(),
+                      stem_ids.data_ptr<int32_t>(), (int)stem_ids.numel(),
+                      stats.data_ptr<int32_t>(), score.data_ptr<double>(), cur_stream());
+  return {stats, score};
 }
 
 // Shadow-copy segments from Python: meta = int64 CPU (n, 8) rows {off, n,

@@ -95,7 +95,7 @@ CiderTables build_cider_tables(const int64_t* labels, int M, int L, const int64_
 
 void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                       const CiderTablesView& t, double log_ref_len, int use_eos,
-                      float* out) {
+                      float* out, bool clipped) {
   std::vector<int> toks;
   std::vector<std::pair<uint64_t, int>> grams;
   for (int i = 0; i < N; ++i) {
@@ -120,10 +120,12 @@ void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
         auto it = vh.find((uint64_t)t.ng_key[g]);
         if (it == vh.end()) continue;
         const double vr = t.ng_val[g];
-        acc[ngram_order((uint64_t)t.ng_key[g]) - 1] += std::min(it->second, vr) * vr;
+        acc[ngram_order((uint64_t)t.ng_key[g]) - 1] +=
+            (clipped ? std::min(it->second, vr) : it->second) * vr;
       }
       const double delta = lh - t.ref_len[r];
-      const double pen = std::exp(-(delta * delta) / 72.0);
+      // (coco CIDEr, clipped = false: no clipping and no length penalty)
+      const double pen = clipped ? std::exp(-(delta * delta) / 72.0) : 1.0;
       for (int n = 0; n < 4; ++n) {
         double val = acc[n];
         const double nr = t.ref_norm[r * 4 + n];

@@ -34,6 +34,7 @@ CiderTables build_cider_tables(const int64_t* labels, int M, int L, const int64_
                                const float* df_vals, int n_df, double log_ref_len, int use_eos);
 
 void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
-                      const CiderTablesView& t, double log_ref_len, int use_eos, float* out);
+                      const CiderTablesView& t, double log_ref_len, int use_eos, float* out,
+                      bool clipped = true);
 
 }  // namespace cst

@@ -11,6 +11,8 @@
 //    counts and fp64 formulas rounded once to fp32.  They are the
 //    backend='cpu' scorer and a second oracle of the GPU kernels
 //    (csrc/kernels/sent_metrics.hip).
+//  * bleu_stats_host / meteor_stats_host: the validation scorer's per-hypothesis
+//    statistics (twins of csrc/kernels/corpus_metrics.hip).
 #include "metric_host.h"
 
 #include <algorithm>
@@ -53,7 +55,8 @@ static void count_ngrams(const std::vector<int>& toks, std::map<uint64_t, int>& 
 }
 
 MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int64_t* start,
-                                 const int64_t* end, int Nv, int use_eos) {
+                                 const int64_t* end, int Nv, int use_eos,
+                                 const int32_t* stem_ids, int V) {
   MetricTables t;
   t.vid_ref_off.resize(Nv + 1);
   t.vid_ng_off.resize(Nv + 1);
@@ -81,6 +84,15 @@ MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int6
       }
       t.ref_len.push_back((int32_t)toks.size());
       t.ref_tok.insert(t.ref_tok.end(), toks.begin(), toks.end());
+      if (stem_ids) {
+        for (int tok : toks) {
+          if (tok >= V)
+            throw std::invalid_argument("reference token id " + std::to_string(tok) +
+                                        " outside the vocabulary of " + std::to_string(V) +
+                                        " stem ids");
+          t.ref_stem.push_back(stem_ids[tok]);
+        }
+      }
       t.ref_tok_off.push_back((int32_t)t.ref_tok.size());
       ++nref;
     }
@@ -104,6 +116,34 @@ static void check_hyps(int T, const int64_t* hyp_video, int N, int Nv) {
                                   " outside the tables");
 }
 
+// correct[4], tlen, rlen of one reduced hypothesis against video v (with
+// references): clipped n-gram matches against the union table, closest
+// reference length with ties to the shorter.
+static void bleu_counts(const std::vector<int>& toks, const MetricTablesView& t, int v,
+                        std::map<uint64_t, int>& grams, int correct[4], int& tlen, int& rlen) {
+  const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
+  count_ngrams(toks, grams);
+  const int64_t* k0 = t.ng_key + t.vid_ng_off[v];
+  const int64_t* k1 = t.ng_key + t.vid_ng_off[v + 1];
+  for (int k = 0; k < 4; ++k) correct[k] = 0;
+  for (auto& g : grams) {
+    // (ascending as uint64: a 4-gram whose last token is >= 32767 has bit 63 set)
+    const int64_t* p = std::lower_bound(
+        k0, k1, (int64_t)g.first,
+        [](int64_t a, int64_t b) { return (uint64_t)a < (uint64_t)b; });
+    if (p != k1 && *p == (int64_t)g.first)
+      correct[ngram_order(g.first) - 1] += std::min(g.second, t.ng_cnt[p - t.ng_key]);
+  }
+  tlen = (int)toks.size();
+  // closest reference length, ties to the shorter: min over (|len_r - tlen|, len_r)
+  int best_d = 1 << 30;
+  rlen = 0;
+  for (int r = r0; r < r1; ++r) {
+    const int d = std::abs(t.ref_len[r] - tlen);
+    if (d < best_d || (d == best_d && t.ref_len[r] < rlen)) best_d = d, rlen = t.ref_len[r];
+  }
+}
+
 void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                       const MetricTablesView& t, int use_eos, float* out) {
   check_hyps(T, hyp_video, N, t.Nv);
@@ -113,36 +153,109 @@ void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
   for (int i = 0; i < N; ++i) {
     reduce_tokens(hyps + (int64_t)i * T, T, use_eos, true, "hypothesis", toks);
     const int v = (int)hyp_video[i];
-    const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
-    if (r1 <= r0) {
+    if (t.vid_ref_off[v + 1] <= t.vid_ref_off[v]) {
       out[i] = 0.f;
       continue;
     }
-    count_ngrams(toks, grams);
-    const int64_t* k0 = t.ng_key + t.vid_ng_off[v];
-    const int64_t* k1 = t.ng_key + t.vid_ng_off[v + 1];
-    int correct[4] = {0, 0, 0, 0};
-    for (auto& g : grams) {
-      // (ascending as uint64: a 4-gram whose last token is >= 32767 has bit 63 set)
-      const int64_t* p = std::lower_bound(
-          k0, k1, (int64_t)g.first,
-          [](int64_t a, int64_t b) { return (uint64_t)a < (uint64_t)b; });
-      if (p != k1 && *p == (int64_t)g.first)
-        correct[ngram_order(g.first) - 1] += std::min(g.second, t.ng_cnt[p - t.ng_key]);
-    }
-    const int tlen = (int)toks.size();
-    // closest reference length, ties to the shorter: min over (|len_r - tlen|, len_r)
-    int best_d = 1 << 30, rlen = 0;
-    for (int r = r0; r < r1; ++r) {
-      const int d = std::abs(t.ref_len[r] - tlen);
-      if (d < best_d || (d == best_d && t.ref_len[r] < rlen)) best_d = d, rlen = t.ref_len[r];
-    }
+    int correct[4], tlen, rlen;
+    bleu_counts(toks, t, v, grams, correct, tlen, rlen);
     double b = 1.0;
     for (int k = 0; k < 4; ++k) b *= (correct[k] + tiny) / (std::max(0, tlen - k) + small);
     double s = std::pow(b, 0.25);
     const double ratio = (tlen + tiny) / (rlen + small);
     if (ratio < 1) s *= std::exp(1 - 1 / ratio);
     out[i] = (float)s;
+  }
+}
+
+void bleu_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                     const MetricTablesView& t, int32_t* out) {
+  check_hyps(T, hyp_video, N, t.Nv);
+  std::vector<int> toks;
+  std::map<uint64_t, int> grams;
+  for (int i = 0; i < N; ++i) {
+    reduce_tokens(hyps + (int64_t)i * T, T, 0, true, "hypothesis", toks);
+    const int v = (int)hyp_video[i];
+    int correct[4] = {0, 0, 0, 0}, tlen = (int)toks.size(), rlen = 0;
+    if (t.vid_ref_off[v + 1] > t.vid_ref_off[v]) bleu_counts(toks, t, v, grams, correct, tlen, rlen);
+    int32_t* o = out + (int64_t)i * 10;
+    for (int k = 0; k < 4; ++k) o[k] = correct[k], o[4 + k] = std::max(0, tlen - k);
+    o[8] = tlen;
+    o[9] = rlen;
+  }
+}
+
+// Meteor._score (eval/metrics.py): alpha .85, beta .2, gamma .6, stem weight .6
+double meteor_score_host(int n_exact, int n_stem, int len_h, int len_r, int chunks) {
+  const int np = n_exact + n_stem;
+  const double m = (double)n_exact + 0.6 * (double)n_stem;
+  if (np <= 0 || len_h <= 0 || len_r <= 0) return 0.0;
+  const double P = m / (double)len_h, R = m / (double)len_r;
+  const double fmean = P * R / (0.85 * P + (1.0 - 0.85) * R);
+  const double frag = (double)chunks / (double)np;
+  const double pen = 0.6 * std::pow(frag, 0.2);
+  return (1.0 - pen) * fmean;
+}
+
+void meteor_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                       const MetricTablesView& t, const int32_t* ref_stem,
+                       const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score) {
+  check_hyps(T, hyp_video, N, t.Nv);
+  std::vector<int> toks, hkey, pair_j;
+  std::vector<char> used;
+  for (int i = 0; i < N; ++i) {
+    reduce_tokens(hyps + (int64_t)i * T, T, 0, false, "hypothesis", toks);
+    const int W = (int)toks.size();
+    const int v = (int)hyp_video[i];
+    const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
+    int best[4] = {0, 0, 0, 0};  // n_exact, n_stem, len_r, chunks
+    double best_score = -1.0;
+    for (int r = r0; r < r1; ++r) {
+      const int o0 = t.ref_tok_off[r];
+      const int n = t.ref_tok_off[r + 1] - o0;
+      pair_j.assign(W, -1);
+      used.assign(n, 0);
+      int cnt[2] = {0, 0};
+      for (int stage = 0; stage < 2; ++stage) {
+        const int32_t* rkey = (stage ? ref_stem : t.ref_tok) + o0;
+        hkey.resize(W);
+        for (int a = 0; a < W; ++a)  // (-1: no stem known, matches nothing)
+          hkey[a] = !stage ? toks[a] : (toks[a] < V ? stem_ids[toks[a]] : -1);
+        for (int a = 0; a < W; ++a) {
+          if (pair_j[a] >= 0 || hkey[a] < 0) continue;
+          int want = 0;
+          for (int p = a - 1; p >= 0; --p)
+            if (pair_j[p] >= 0) {
+              want = pair_j[p] + 1;
+              break;
+            }
+          int bj = -1, bd = 1 << 30;
+          for (int j = 0; j < n; ++j) {  // (ascending j: the smaller j on equal distance)
+            if (used[j] || rkey[j] != hkey[a]) continue;
+            const int d = std::abs(j - want);
+            if (d < bd) bd = d, bj = j;
+          }
+          if (bj < 0) continue;
+          used[bj] = 1;
+          pair_j[a] = bj;
+          cnt[stage] += 1;
+        }
+      }
+      int chunks = 0;
+      for (int a = 0; a < W; ++a)
+        if (pair_j[a] >= 0 && !(a > 0 && pair_j[a - 1] >= 0 && pair_j[a - 1] + 1 == pair_j[a]))
+          ++chunks;
+      const double sc = meteor_score_host(cnt[0], cnt[1], W, n, chunks);
+      if (sc > best_score) {
+        best_score = sc;
+        best[0] = cnt[0], best[1] = cnt[1], best[2] = n, best[3] = chunks;
+      }
+    }
+    int32_t* o = out_stats + (int64_t)i * 6;
+    const bool any = r1 > r0;
+    o[0] = best[0], o[1] = best[1], o[2] = any ? W : 0, o[3] = best[2], o[4] = best[3];
+    o[5] = best[0] + best[1];
+    out_score[i] = any ? best_score : 0.0;
   }
 }
 

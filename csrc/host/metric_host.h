@@ -22,6 +22,9 @@ struct MetricTables {
   // ROUGE: the reduced reference token rows, ragged
   std::vector<int32_t> ref_tok_off;  // (nref + 1)
   std::vector<int32_t> ref_tok;
+  // METEOR (validation scorer): the stem id of every ref_tok entry; filled
+  // only when the builder is given the vocabulary's stem ids
+  std::vector<int32_t> ref_stem;
 };
 
 struct MetricTablesView {
@@ -43,8 +46,11 @@ inline MetricTablesView view_of(const MetricTables& t) {
 
 // Throws std::invalid_argument when a reference is longer than METRIC_MAXT
 // tokens or holds a token outside [0, METRIC_MAX_TOKEN].
+// stem_ids (V entries, optional): also fills ref_stem; a reference token >= V
+// is then rejected too.
 MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int64_t* start,
-                                 const int64_t* end, int Nv, int use_eos);
+                                 const int64_t* end, int Nv, int use_eos,
+                                 const int32_t* stem_ids = nullptr, int V = 0);
 
 // (N, T) hypotheses, T <= METRIC_MAXT (std::invalid_argument otherwise; BLEU
 // also rejects tokens above METRIC_MAX_TOKEN).  A video without references
@@ -53,5 +59,20 @@ void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
                       const MetricTablesView& t, int use_eos, float* out);
 void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                         const MetricTablesView& t, int use_eos, float* out);
+
+// Validation scorer (ops/corpus_metrics.py), fp64 host twins of
+// csrc/kernels/corpus_metrics.hip.  Hypotheses are reduced without EOS.
+//  * bleu_stats_host: per hypothesis correct[4], guess[4], tlen, rlen (10 ints),
+//    the summands of Bleu.compute_score's corpus value;
+//  * meteor_stats_host: Meteor._align / _stats of the best reference by
+//    Meteor._score (the first on ties): n_exact, n_stem, len_h, len_r, chunks,
+//    n_pairs (6 ints) and the segment score.  ref_stem is the table's stem row,
+//    stem_ids the V stem ids of the vocabulary.
+void bleu_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                     const MetricTablesView& t, int32_t* out);
+void meteor_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
+                       const MetricTablesView& t, const int32_t* ref_stem,
+                       const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score);
+double meteor_score_host(int n_exact, int n_stem, int len_h, int len_r, int chunks);
 
 }  // namespace cst

@@ -29,7 +29,11 @@ constexpr int CIDER_MAXT = 64;
 
 // One 256-thread block per hypothesis: wave 0 builds the hypothesis vector
 // (steps 1-3) in LDS, then the 4 waves split the video's references.
-__global__ __launch_bounds__(256) void cider_d_kernel(
+// CLIPPED: CIDEr-D (min(vh, vr) * vr and the Gaussian length penalty).  false:
+// coco CIDEr, the validation metric (vh * vr, penalty 1; csrc/kernels/
+// corpus_metrics.hip describes the validation scorer).
+template <bool CLIPPED>
+__device__ __forceinline__ void cider_body(
     const int64_t* __restrict__ hyps, int T, const int64_t* __restrict__ hyp_video, int N,
     const int64_t* __restrict__ ht_keys, const float* __restrict__ ht_vals, uint32_t ht_cap,
     const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_ng_off,
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(256) void cider_d_kernel(
       const int cnt = W - n;
       float c = 0.f;
       for (int j = 0; j < cnt; ++j) {
-        if (s_key[n][j] == key) c += fminf(s_val[n][j], vr) * vr;
+        if (s_key[n][j] == key) c += (CLIPPED ? fminf(s_val[n][j], vr) : s_val[n][j]) * vr;
       }
       acc0 += n == 0 ? c : 0.f;
       acc1 += n == 1 ? c : 0.f;
@@ -112,8 +116,11 @@ __global__ __launch_bounds__(256) void cider_d_kernel(
       acc3 += n == 3 ? c : 0.f;
     }
     const float acc[4] = {wave_sum(acc0), wave_sum(acc1), wave_sum(acc2), wave_sum(acc3)};
-    const float delta = len_h - (float)ref_len[r];
-    const float pen = __expf(-(delta * delta) / 72.f);
+    float pen = 1.f;
+    if (CLIPPED) {
+      const float delta = len_h - (float)ref_len[r];
+      pen = __expf(-(delta * delta) / 72.f);
+    }
     float s = 0.f;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
@@ -133,6 +140,28 @@ __global__ __launch_bounds__(256) void cider_d_kernel(
   }
 }
 
+__global__ __launch_bounds__(256) void cider_d_kernel(
+    const int64_t* __restrict__ hyps, int T, const int64_t* __restrict__ hyp_video, int N,
+    const int64_t* __restrict__ ht_keys, const float* __restrict__ ht_vals, uint32_t ht_cap,
+    const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_ng_off,
+    const float* __restrict__ ref_norm, const int32_t* __restrict__ ref_len,
+    const int64_t* __restrict__ ng_key, const float* __restrict__ ng_val, float log_ref_len,
+    int use_eos, float* __restrict__ out) {
+  cider_body<true>(hyps, T, hyp_video, N, ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off,
+                   ref_norm, ref_len, ng_key, ng_val, log_ref_len, use_eos, out);
+}
+
+__global__ __launch_bounds__(256) void cider_unclipped_kernel(
+    const int64_t* __restrict__ hyps, int T, const int64_t* __restrict__ hyp_video, int N,
+    const int64_t* __restrict__ ht_keys, const float* __restrict__ ht_vals, uint32_t ht_cap,
+    const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_ng_off,
+    const float* __restrict__ ref_norm, const int32_t* __restrict__ ref_len,
+    const int64_t* __restrict__ ng_key, const float* __restrict__ ng_val, float log_ref_len,
+    int use_eos, float* __restrict__ out) {
+  cider_body<false>(hyps, T, hyp_video, N, ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off,
+                    ref_norm, ref_len, ng_key, ng_val, log_ref_len, use_eos, out);
+}
+
 void launch_cider_d(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
                     const int64_t* ht_keys, const float* ht_vals, uint32_t ht_cap,
                     const int32_t* vid_ref_off, const int32_t* ref_ng_off,
@@ -145,6 +174,21 @@ void launch_cider_d(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
                      ht_vals, ht_cap, vid_ref_off, ref_ng_off, ref_norm, ref_len, ng_key,
                      ng_val, log_ref_len, use_eos, out);
   post_launch("cider_d_kernel", stream);
+}
+
+// coco CIDEr (unclipped, no length penalty) on the same tables; T <= 64.
+void launch_cider_unclipped(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
+                            const int64_t* ht_keys, const float* ht_vals, uint32_t ht_cap,
+                            const int32_t* vid_ref_off, const int32_t* ref_ng_off,
+                            const float* ref_norm, const int32_t* ref_len,
+                            const int64_t* ng_key, const float* ng_val, float log_ref_len,
+                            int use_eos, float* out, hipStream_t stream) {
+  if (N <= 0) return;
+  dim3 grid(N), block(256);
+  hipLaunchKernelGGL(cider_unclipped_kernel, grid, block, 0, stream, hyps, T, hyp_video, N,
+                     ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off, ref_norm, ref_len, ng_key,
+                     ng_val, log_ref_len, use_eos, out);
+  post_launch("cider_unclipped_kernel", stream);
 }
 
 }  // namespace cst

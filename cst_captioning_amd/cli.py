@@ -108,6 +108,8 @@ def train_main(argv=None):
     model, engine = build_model(opt, dev)
     from .train.trainer import Trainer
     trainer = Trainer(opt, model, train_loader, val_loader, ctx, engine)
+    if opt.result_file:  # (--val_scorer tokens: refuse an unscorable test split before training)
+        trainer.check_val_scorer(test_loader)
     start = datetime.now()
     infos = trainer.train()
     logger.info('Best val %s score: %f. Best iter: %d. Best epoch: %d', opt.eval_metric,
@@ -140,6 +142,8 @@ def test_main(argv=None):
                                             opt.num_chunks,
                                             cocofmt_file=opt.test_cocofmt_file)
     loader = CaptionLoader(te, opt.test_batch_size, opt.test_seq_per_img, 'test', ctx.device)
+    from .train.trainer import Trainer, check_val_scorer
+    check_val_scorer(opt, loader)
     assert opt.vocab_size == loader.get_vocab_size()
     assert opt.seq_length == loader.get_seq_length()
     assert list(opt.feat_dims) == list(loader.get_feat_dims())
@@ -147,7 +151,6 @@ def test_main(argv=None):
     model.load_state_dict(ck['model'])
     if engine is not None:
         engine.refresh_weights()
-    from .train.trainer import Trainer
     res = Trainer(opt, model, loader, None, ctx, engine).test(loader)
     ctx.destroy()
     return res

@@ -102,6 +102,10 @@ def build_parser():
              'accumulation / master weights); fp32 = PyTorch path in fp32')
     add('--reward_device', type=str, default='gpu', choices=['gpu', 'cpu'],
         help='CIDEr-D reward: on-GPU HIP kernel, or the CPU scorer (reference semantics)')
+    add('--val_scorer', type=str, default='strings', choices=['strings', 'tokens'],
+        help='validation / test metrics: strings = decoded sentences through the Python '
+             'scorers (reference route); tokens = token ids against the split\'s label table, '
+             'on the GPU when the model runs there (ops/corpus_metrics.py)')
     add('--mask_after_eos', type=int, default=0,
         help='fix for SURVEY §2.8.1: mask MIXER tokens sampled after EOS (0 = reference parity)')
     add('--dedupe_greedy', type=int, default=1,

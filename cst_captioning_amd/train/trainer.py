@@ -79,6 +79,22 @@ def build_scorer(opt, dataset, device):
     return GenericScorer(dataset, Meteor(), opt.use_eos)  # (needs the stemmer: CPU only)
 
 
+def check_val_scorer(opt, loader):
+    """``--val_scorer tokens`` scores against the label table through the
+    native extension: raises ``ValueError`` for a split that cannot be scored,
+    so that set-up fails and not the first validation.  No-op with
+    ``strings`` or without a loader."""
+    if getattr(opt, 'val_scorer', 'strings') != 'tokens' or loader is None:
+        return
+    from .. import _ext
+    if not loader.has_label:
+        raise ValueError('--val_scorer tokens scores against the label table, but the '
+                         'evaluated split has no labels')
+    if not _ext.host_available():
+        raise ValueError('--val_scorer tokens needs the native extension, which is not '
+                         'built (python setup.py build_ext --inplace)')
+
+
 class Trainer:
     def __init__(self, opt, model, train_loader, val_loader=None, ctx=None, engine=None):
         from ..parallel import DistContext
@@ -167,6 +183,10 @@ class Trainer:
                       'best_iter': 0, 'best_epoch': opt.max_epochs}
         self.history = {}
         self.rl_training = False
+        # --val_scorer tokens: one CorpusScorer per evaluated loader, built at
+        # its first scoring; that the split can be scored is checked up front
+        self._corpus_scorers = {}
+        self.check_val_scorer(val_loader)
         # HIP-graph step (see graph_step): captured step per schedule key
         self._graph = None
         self._graph_key = None
@@ -772,51 +792,60 @@ class Trainer:
             logger.info('%s', '\t'.join('{}: {}'.format(k, v) for k, v in items))
 
     # ----------------------------------------------------------- validate ---
-    @torch.no_grad()
-    def validate(self, loader):
-        opt, m, ctx = self.opt, self.model, self.ctx
-        m.eval()
-        n_videos = loader.get_num_videos()
-        bsz = loader.get_batch_size()
-        n_iters = int(math.ceil(n_videos / bsz))
-        S = loader.get_seq_per_img()
-        m.set_seq_per_img(S)
-        local = {'pred': [], 'loss': [], 'gt_avglogp': [], 'test_avglogp': []}
-        for ii in range(ctx.rank, n_iters, ctx.world_size):  # C4: batches sharded over ranks
-            data = loader.get_batch_at(ii)
-            if loader.has_label:
-                if self.engine is not None:
-                    lp = self.engine.teacher_forced(m, data['feats'], data['labels'])
-                    loss = self.xe_criterion(lp, data['labels'][:, 1:], data['masks'][:, 1:])
-                    gt_seq, gt_lp = data['labels'][:, 1:lp.size(1) + 1], lp
-                else:
-                    pred, gt_seq, gt_lp = m(data['feats'], data['labels'])
-                    loss = self.xe_criterion(pred, data['labels'][:, 1:], data['masks'][:, 1:])
-                local['loss'].append((ii, float(loss)))
-                if opt.output_logp == 1:
-                    local['gt_avglogp'].append(
-                        (ii, compute_avglogp(gt_seq.cpu().numpy(), gt_lp.cpu().numpy())))
-            seq, logseq = m.sample(data['feats'], {'beam_size': opt.beam_size})
-            seq, logseq = seq.cpu().numpy(), logseq.cpu().numpy()
-            sents = decode_sequence(loader.get_vocab(), seq)
-            avg = compute_avglogp(seq, logseq) if opt.output_logp == 1 else None
-            for jj, sent in enumerate(sents):
-                e = {'image_id': data['ids'][jj], 'caption': sent}
-                if avg is not None:
-                    e['avglogp'] = avg[jj]
-                local['pred'].append((ii, jj, e))
-                logger.debug('[%d] video %s: %s', jj, e['image_id'], sent)
+    def check_val_scorer(self, loader):
+        check_val_scorer(self.opt, loader)
+
+    def corpus_scorer(self, loader):
+        """The token-space validation scorer of ``loader``'s split
+        (``--val_scorer tokens``), built on first use and once per loader.
+        Only the main rank scores, so only it builds the tables."""
+        key = id(loader)
+        if key not in self._corpus_scorers:
+            self.check_val_scorer(loader)
+            scorer = None
+            if self.ctx.is_main:
+                from ..ops.corpus_metrics import CorpusScorer
+                scorer = CorpusScorer(loader.ds, self.device, 'auto')
+            self._corpus_scorers[key] = (loader, scorer)  # (keeps the loader: ids stay unique)
+        return self._corpus_scorers[key][1]
+
+    def _val_loss(self, data):
+        """Teacher-forced XE loss of one validation batch and what the GT
+        avglogp needs: (loss, gt_seq, gt_logprobs), all on the device."""
+        m = self.model
+        if self.engine is not None:
+            lp = self.engine.teacher_forced(m, data['feats'], data['labels'])
+            loss = self.xe_criterion(lp, data['labels'][:, 1:], data['masks'][:, 1:])
+            return loss, data['labels'][:, 1:lp.size(1) + 1], lp
+        pred, gt_seq, gt_lp = m(data['feats'], data['labels'])
+        loss = self.xe_criterion(pred, data['labels'][:, 1:], data['masks'][:, 1:])
+        return loss, gt_seq, gt_lp
+
+    @staticmethod
+    def _val_entries(local, ii, ids, sents, avg):
+        """Appends batch ``ii``'s prediction entries (``avg``: the rows'
+        avglogp, or None) to ``local['pred']``."""
+        for jj, sent in enumerate(sents):
+            e = {'image_id': ids[jj], 'caption': sent}
+            if avg is not None:
+                e['avglogp'] = avg[jj]
+            local['pred'].append((ii, jj, e))
+            logger.debug('[%d] video %s: %s', jj, e['image_id'], sent)
+
+    def _val_results(self, local, n_iters, S, metrics):
+        """The part of validation after the batch loop: gather the ranks'
+        predictions and losses, score on the main rank (``metrics(predictions,
+        gathered)`` -> dict, called only there and only with language_eval),
+        avglogp outputs, broadcast of the scores."""
+        opt, ctx = self.opt, self.ctx
         gathered = ctx.all_gather_object(local)
         preds = sorted((p for g in gathered for p in g['pred']), key=lambda x: (x[0], x[1]))
         predictions = [p[2] for p in preds]
         losses = [l for g in gathered for _, l in g['loss']]
         results = {'predictions': predictions}
         scores = {'Loss': -round(sum(losses) / n_iters, 3) if losses else 0.0}
-        if ctx.is_main and opt.language_eval == 1 and loader.has_label:
-            from ..eval import language_eval
-            refs = loader.ds.refs()
-            if refs:
-                scores.update(language_eval(refs, predictions))
+        if ctx.is_main and opt.language_eval == 1:
+            scores.update(metrics(predictions, gathered))
         if opt.output_logp == 1:
             ta = [p['avglogp'] for p in predictions]
             scores['avglogp'] = sum(ta) / len(ta)
@@ -832,6 +861,124 @@ class Trainer:
                 np.save(path[:-4] + '.npy', gt)
                 logger.info('Wrote GT logp to: %s', path)
         results['scores'] = ctx.broadcast_object(scores)
+        return results
+
+    @torch.no_grad()
+    def _validate_tokens(self, loader):
+        """:meth:`validate` with ``--val_scorer tokens``.  Inside the loop the
+        decoded sequences and the losses stay on the device and nothing
+        synchronises with the host (the batches' video indices are host arrays
+        of the loader and stay there).  After it the sequences and the losses
+        are copied to the host once each, for the prediction strings and the
+        reported loss; the metrics come from
+        :class:`..ops.corpus_metrics.CorpusScorer` on the token ids, which
+        uploads the video indices, synchronises for its two input checks and
+        copies its five per-hypothesis result arrays back."""
+        opt, m, ctx = self.opt, self.model, self.ctx
+        self.check_val_scorer(loader)
+        m.eval()
+        n_videos = loader.get_num_videos()
+        bsz = loader.get_batch_size()
+        n_iters = int(math.ceil(n_videos / bsz))
+        S = loader.get_seq_per_img()
+        m.set_seq_per_img(S)
+        want_logp = opt.output_logp == 1
+        its, seqs, logseqs, vids, ids, losses, gt_pairs = [], [], [], [], [], [], []
+        for ii in range(ctx.rank, n_iters, ctx.world_size):  # C4: batches sharded over ranks
+            data = loader.get_batch_at(ii)
+            loss, gt_seq, gt_lp = self._val_loss(data)
+            losses.append(loss.detach().reshape(()))
+            if want_logp:
+                gt_pairs.append((gt_seq, gt_lp))
+            seq, logseq = m.sample(data['feats'], {'beam_size': opt.beam_size})
+            its.append(ii)
+            seqs.append(seq)
+            vids.append(data['vids'])
+            ids.append(data['ids'])
+            if want_logp:
+                logseqs.append(logseq)
+        # after the loop: the batches padded to one width, one copy each of the
+        # sequences, the losses and (with output_logp) the log-probabilities
+        widths = [s.size(1) for s in seqs]
+        width = max(widths or [0])
+        seqs = [torch.nn.functional.pad(s, (0, width - s.size(1))) for s in seqs]
+        seq_dev = torch.cat(seqs) if seqs else torch.zeros(0, 0, dtype=torch.long)
+        seq_host = seq_dev.cpu().numpy()
+        loss_host = torch.stack(losses).cpu().tolist() if losses else []
+        vid_host = np.concatenate(vids) if vids else np.zeros(0, np.int64)
+        sents = decode_sequence(loader.get_vocab(), seq_host)
+        logseq_host = None
+        if want_logp and logseqs:
+            logseq_host = torch.cat([torch.nn.functional.pad(l, (0, width - l.size(1)))
+                                     for l in logseqs]).cpu().numpy()
+        local = {'pred': [], 'loss': list(zip(its, loss_host)), 'gt_avglogp': [],
+                 'tok': (seq_host, vid_host)}
+        row = 0
+        for ii, batch_ids, w in zip(its, ids, widths):
+            n = len(batch_ids)
+            # (avglogp over the batch's own width: a row without EOS must not
+            # run on into the padding)
+            avg = None if logseq_host is None else compute_avglogp(
+                seq_host[row:row + n, :w], logseq_host[row:row + n, :w])
+            self._val_entries(local, ii, batch_ids, sents[row:row + n], avg)
+            row += n
+        for ii, (gt_seq, gt_lp) in zip(its, gt_pairs):
+            local['gt_avglogp'].append(
+                (ii, compute_avglogp(gt_seq.cpu().numpy(), gt_lp.cpu().numpy())))
+
+        def metrics(predictions, gathered):
+            if ctx.world_size == 1:
+                tok, vid = seq_dev, torch.from_numpy(vid_host)
+            else:  # (rows in any order: every row carries its video index)
+                w = max(g['tok'][0].shape[1] for g in gathered)
+                tok = torch.from_numpy(np.concatenate(
+                    [np.pad(g['tok'][0], ((0, 0), (0, w - g['tok'][0].shape[1])))
+                     for g in gathered]))
+                vid = torch.from_numpy(np.concatenate([g['tok'][1] for g in gathered]))
+            out = self.corpus_scorer(loader).score(tok, vid)
+            return {k: round(v, 5) for k, v in out['scores'].items()}
+
+        results = self._val_results(local, n_iters, S, metrics)
+        # this rank's decoded token rows and their dataset video indices
+        results['sequences'] = seq_host
+        results['video_index'] = vid_host
+        m.train()
+        return results
+
+    @torch.no_grad()
+    def validate(self, loader):
+        if getattr(self.opt, 'val_scorer', 'strings') == 'tokens':
+            return self._validate_tokens(loader)
+        opt, m, ctx = self.opt, self.model, self.ctx
+        m.eval()
+        n_videos = loader.get_num_videos()
+        bsz = loader.get_batch_size()
+        n_iters = int(math.ceil(n_videos / bsz))
+        S = loader.get_seq_per_img()
+        m.set_seq_per_img(S)
+        local = {'pred': [], 'loss': [], 'gt_avglogp': [], 'test_avglogp': []}
+        for ii in range(ctx.rank, n_iters, ctx.world_size):  # C4: batches sharded over ranks
+            data = loader.get_batch_at(ii)
+            if loader.has_label:
+                loss, gt_seq, gt_lp = self._val_loss(data)
+                local['loss'].append((ii, float(loss)))
+                if opt.output_logp == 1:
+                    local['gt_avglogp'].append(
+                        (ii, compute_avglogp(gt_seq.cpu().numpy(), gt_lp.cpu().numpy())))
+            seq, logseq = m.sample(data['feats'], {'beam_size': opt.beam_size})
+            seq, logseq = seq.cpu().numpy(), logseq.cpu().numpy()
+            sents = decode_sequence(loader.get_vocab(), seq)
+            avg = compute_avglogp(seq, logseq) if opt.output_logp == 1 else None
+            self._val_entries(local, ii, data['ids'], sents, avg)
+
+        def metrics(predictions, gathered):
+            if not loader.has_label:
+                return {}
+            from ..eval import language_eval
+            refs = loader.ds.refs()
+            return language_eval(refs, predictions) if refs else {}
+
+        results = self._val_results(local, n_iters, S, metrics)
         m.train()
         return results
 
@@ -841,7 +988,8 @@ class Trainer:
             logger.info('Test output: %s', json.dumps(results['scores'], indent=4))
             if self.opt.result_file:
                 with open(self.opt.result_file, 'w') as f:
-                    json.dump(results, f)
+                    # (--val_scorer tokens also returns the token arrays: not written)
+                    json.dump({k: results[k] for k in ('predictions', 'scores')}, f)
                 logger.info('Wrote output caption to: %s ', self.opt.result_file)
         return results
 
