@@ -1,127 +1,12 @@
 // Python bindings of the native extension cst_captioning_amd._C.
 #include <torch/extension.h>
 
+#include "engine.h"
 #include "host/cider_host.h"
 #include "host/metric_host.h"
 #include "launchers.h"
 
 namespace cst {
-std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tensor ptab,
-                                        at::Tensor whh, at::Tensor wlog,
-                                        at::Tensor blog, at::Tensor vgate, int64_t vgate_div,
-                                        at::Tensor labels, at::Tensor bos, int64_t R, int64_t T,
-                                        std::vector<int64_t> modes, double ss_prob,
-                                        double drop_p, double temperature, at::Tensor rng,
-                                        bool save, bool want_xe, bool use_counts,
-                                        bool use_unfinished, std::vector<at::Tensor> att,
-                                        int64_t cell, std::vector<at::Tensor> state0,
-                                        std::vector<at::Tensor> up, bool store_exp,
-                                        bool xe_rows, c10::optional<at::Tensor> lab_idx);
-void set_grad_events(bool on);
-void grad_event_wait(int64_t k, int64_t stream);
-void grad_event_record(int64_t k, int64_t stream);
-int64_t grad_event_count(int64_t k);
-void set_poll_bound(int64_t n);
-void set_bwd_loop(int64_t mode);
-void set_att_fuse(bool on);
-double lstm_bwd_loop_bench(int64_t R, int64_t H, int64_t T, int64_t iters, at::Tensor phases,
-                           int64_t dbg);
-int64_t device_errors(int64_t dev_index);
-void reset_device_errors(int64_t dev_index);
-void gemm_bf16_tuned(at::Tensor out, at::Tensor a, bool ta, at::Tensor b, bool tb,
-                     int64_t n_cand);
-void gemm_bf16_tuned_batched(at::Tensor out, at::Tensor a, bool ta, at::Tensor b, bool tb,
-                             int64_t n_cand);
-std::vector<double> gemm_tuned_timings(at::Tensor out, at::Tensor a, bool ta, at::Tensor b,
-                                       bool tb);
-std::vector<std::vector<double>> gemm_tuned_choices();
-std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Tensor emb,
-                                         at::Tensor lse, at::Tensor logits16,
-                                         at::Tensor hdrop_all, at::Tensor gates_all,
-                                         at::Tensor c_all, at::Tensor h_all, at::Tensor seq,
-                                         at::Tensor labels, at::Tensor toks, at::Tensor dg_sel,
-                                         at::Tensor dg_xe, double drop_p, at::Tensor rng,
-                                         at::Tensor out_wlog, at::Tensor out_blog,
-                                         int64_t comm_stream, std::vector<at::Tensor> att,
-                                         at::Tensor out_emb, at::Tensor ds_bias, int64_t cell,
-                                         std::vector<at::Tensor> state0,
-                                         std::vector<at::Tensor> up, at::Tensor blog,
-                                         at::Tensor fix_total, int64_t vgate_div,
-                                         at::Tensor xw, std::vector<at::Tensor> vg_bwd,
-                                         int64_t vg_nf, double vg_p, int64_t x_wait,
-                                         bool exp_zero_off, std::vector<at::Tensor> dw_slots,
-                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C);
-std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor whh,
-                                    at::Tensor wlog, at::Tensor blog, at::Tensor vgate,
-                                    int64_t K, int64_t T, int64_t bos_index,
-                                    std::vector<at::Tensor> att, int64_t cell,
-                                    std::vector<at::Tensor> state0, std::vector<at::Tensor> up);
-double vgrad_colsum_bench(at::Tensor E, at::Tensor alpha, int64_t V, int64_t iters);
-double token_sort_bench(at::Tensor toks, int64_t V, int64_t iters);
-double att_bench(at::Tensor gv, at::Tensor P, at::Tensor q, at::Tensor wa, at::Tensor ba,
-                 int64_t R, int64_t which, int64_t iters);
-std::vector<at::Tensor> token_sort(at::Tensor toks, int64_t V);
-at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V);
-std::vector<at::Tensor> cst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor scores,
-                                         at::Tensor bref, int64_t S, int64_t k);
-std::vector<at::Tensor> scst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor sample,
-                                          at::Tensor greedy);
-std::vector<at::Tensor> xe_loss_forward(at::Tensor labels, at::Tensor lp, int64_t off);
-at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, int64_t T);
-at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
-                              at::Tensor dloss);
-at::Tensor featpool_forward(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
-                            std::vector<at::Tensor> bs, double drop_p, at::Tensor rng,
-                            c10::optional<at::Tensor> idx, int64_t C);
-std::vector<at::Tensor> featpool_forward16(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
-                                           std::vector<at::Tensor> bs, double drop_p,
-                                           at::Tensor rng, c10::optional<at::Tensor> idx,
-                                           int64_t C);
-std::vector<at::Tensor> featpool_backward(at::Tensor dout, at::Tensor out,
-                                          std::vector<at::Tensor> xs,
-                                          std::vector<at::Tensor> ws, double drop_p,
-                                          std::vector<at::Tensor> outs,
-                                          c10::optional<at::Tensor> idx, int64_t C);
-std::vector<at::Tensor> att_mfma_fwd(at::Tensor h, at::Tensor wq, at::Tensor P, at::Tensor wa,
-                                     at::Tensor ba, at::Tensor gv,
-                                     int64_t whole);
-std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor wlog,
-                                         at::Tensor blog, at::Tensor whh, at::Tensor vgate,
-                                         int64_t vdiv, at::Tensor tgt, at::Tensor eoff,
-                                         int64_t save, int64_t mode, int64_t step, at::Tensor rng,
-                                         at::Tensor ptab, at::Tensor c_prev, double drop_p,
-                                         int64_t cell, int64_t eos, at::Tensor unfinished,
-                                         double ss_prob);
-std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor blog,
-                                     at::Tensor rng, int64_t mode, double temperature,
-                                     int64_t step);
-double vocab_fwd_bench(at::Tensor hd, at::Tensor wlog, at::Tensor blog, at::Tensor tgt,
-                       int64_t flags, bool save, int64_t iters, int64_t variant);
-at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                       double log_ref_len, int64_t use_eos, bool clipped);
-at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t);
-std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
-                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids);
-at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
-                        std::map<std::string, at::Tensor> t, int64_t use_eos);
-at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
-                          at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
-                          double b1, double b2, double eps, double clip, double gscale,
-                          int64_t phase, at::Tensor shadow_meta,
-                          std::vector<at::Tensor> shadow_dst);
-void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tensor> shadow_dst);
-void set_stamp_base(int64_t base);
-void stamp_buffer(at::Tensor buf);
-void stamp_now(int64_t slot);
-void busy_copy(at::Tensor buf, int64_t blocks, double us, int64_t stream);
-int64_t wall_clock_khz();
-void vocab_x(at::Tensor logits16, at::Tensor wlog, at::Tensor out);
-at::Tensor att_mfma_phases(at::Tensor gv, at::Tensor P, at::Tensor wa, at::Tensor ba, int64_t R);
-at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K);
-void wgrad_tn_rows(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K, at::Tensor out,
-                   at::Tensor rmap);
-std::vector<at::Tensor> wgrad_tn_colsum(at::Tensor A, at::Tensor B, at::Tensor al, int64_t M,
-                                        int64_t N, int64_t K);
 
 template <class T>
 static at::Tensor to_tensor(const std::vector<T>& v, at::ScalarType st) {
@@ -153,6 +38,15 @@ static std::map<std::string, at::Tensor> cider_build_tables(at::Tensor labels, a
           {"ref_len", to_tensor(t.ref_len, at::kInt)},
           {"ng_key", to_tensor(t.ng_key, at::kLong)},
           {"ng_val", to_tensor(t.ng_val, at::kFloat)}};
+}
+
+// the CPU scorers' hypotheses: hyps (N, T), hyp_video (N), as contiguous int64
+static void cpu_hyps(at::Tensor& hyps, at::Tensor& hyp_video) {
+  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
+                  hyp_video.size(0) == hyps.size(0),
+              "CPU hyps (N, T) and hyp_video (N)");
+  hyps = hyps.contiguous().to(at::kLong);
+  hyp_video = hyp_video.contiguous().to(at::kLong);
 }
 
 static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
@@ -206,30 +100,6 @@ static std::map<std::string, at::Tensor> metric_build_tables(
   return out;
 }
 
-static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
-                                   at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                                   int64_t use_eos) {
-  const bool bleu = metric == "Bleu_4";
-  TORCH_CHECK(bleu || metric == "ROUGE_L", "metric_score_cpu: metric must be Bleu_4 or ROUGE_L, got ",
-              metric);
-  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
-                  hyp_video.size(0) == hyps.size(0),
-              "CPU hyps (N, T) and hyp_video (N)");
-  hyps = hyps.contiguous().to(at::kLong);
-  hyp_video = hyp_video.contiguous().to(at::kLong);
-  MetricTablesView v{(int)t.at("vid_ref_off").numel() - 1,
-                     t.at("vid_ref_off").data_ptr<int32_t>(), t.at("ref_len").data_ptr<int32_t>(),
-                     t.at("vid_ng_off").data_ptr<int32_t>(), t.at("ng_key").data_ptr<int64_t>(),
-                     t.at("ng_cnt").data_ptr<int32_t>(), t.at("ref_tok_off").data_ptr<int32_t>(),
-                     t.at("ref_tok").data_ptr<int32_t>()};
-  at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
-  (bleu ? bleu4_score_host : rouge_l_score_host)(
-      hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
-      hyp_video.data_ptr<int64_t>(), v, (int)use_eos, out.data_ptr<float>());
-  return out;
-}
-
-// Validation scorer on the CPU: the host twins of kernels/corpus_metrics.hip.
 static MetricTablesView metric_view(std::map<std::string, at::Tensor>& t) {
   return {(int)t.at("vid_ref_off").numel() - 1,
           t.at("vid_ref_off").data_ptr<int32_t>(), t.at("ref_len").data_ptr<int32_t>(),
@@ -238,13 +108,24 @@ static MetricTablesView metric_view(std::map<std::string, at::Tensor>& t) {
           t.at("ref_tok").data_ptr<int32_t>()};
 }
 
+static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
+                                   at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
+                                   int64_t use_eos) {
+  const bool bleu = metric == "Bleu_4";
+  TORCH_CHECK(bleu || metric == "ROUGE_L", "metric_score_cpu: metric must be Bleu_4 or ROUGE_L, got ",
+              metric);
+  cpu_hyps(hyps, hyp_video);
+  at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
+  (bleu ? bleu4_score_host : rouge_l_score_host)(
+      hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
+      hyp_video.data_ptr<int64_t>(), metric_view(t), (int)use_eos, out.data_ptr<float>());
+  return out;
+}
+
+// Validation scorer on the CPU: the host twins of kernels/corpus_metrics.hip.
 static at::Tensor bleu_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                  std::map<std::string, at::Tensor> t) {
-  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
-                  hyp_video.size(0) == hyps.size(0),
-              "CPU hyps (N, T) and hyp_video (N)");
-  hyps = hyps.contiguous().to(at::kLong);
-  hyp_video = hyp_video.contiguous().to(at::kLong);
+  cpu_hyps(hyps, hyp_video);
   at::Tensor out = at::empty({hyps.size(0), 10}, at::TensorOptions().dtype(at::kInt));
   bleu_stats_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
                   hyp_video.data_ptr<int64_t>(), metric_view(t), out.data_ptr<int32_t>());
@@ -254,13 +135,9 @@ static at::Tensor bleu_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
 static std::vector<at::Tensor> meteor_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                                 std::map<std::string, at::Tensor> t,
                                                 at::Tensor stem_ids) {
-  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2 && hyp_video.dim() == 1 &&
-                  hyp_video.size(0) == hyps.size(0),
-              "CPU hyps (N, T) and hyp_video (N)");
+  cpu_hyps(hyps, hyp_video);
   TORCH_CHECK(t.count("ref_stem") && t.at("ref_stem").numel() == t.at("ref_tok").numel(),
               "metric tables were built without stem ids");
-  hyps = hyps.contiguous().to(at::kLong);
-  hyp_video = hyp_video.contiguous().to(at::kLong);
   stem_ids = stem_ids.contiguous().to(at::kInt);
   at::Tensor stats = at::empty({hyps.size(0), 6}, at::TensorOptions().dtype(at::kInt));
   at::Tensor score = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kDouble));

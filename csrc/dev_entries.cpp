@@ -1,0 +1,504 @@
+// Entries that exist only for tests and microbenchmarks.
+#include "engine_internal.h"
+
+namespace cst {
+
+// microbenchmark of the persistent reverse loop alone (random operands of the
+// given shape): mean us per launch over `iters` launches; `phases` (int64,
+// grid x T x 4, nullable-empty) receives the last launch's per-step stamps
+// (step start, team wait done, operands + GEMM done, step published)
+double lstm_bwd_loop_bench(int64_t R, int64_t H, int64_t T, int64_t iters, at::Tensor phases,
+                           int64_t dbg) {
+  TORCH_CHECK(lstm_bwd_loop_ok((int)R, (int)H, (int)T), "lstm_bwd_loop_bench: unsupported shape");
+  auto dev = at::Device(at::kCUDA, at::hip::getCurrentHIPStream().device_index());
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+  auto b16 = at::TensorOptions().dtype(at::kBFloat16).device(dev);
+  at::Tensor dG = at::empty({T, R, 4 * H}, b16);
+  at::Tensor whhT = (at::randn({H, 4 * H}, f32) * 0.05).to(at::kBFloat16);
+  at::Tensor dh = at::randn({T, R, H}, f32) * 0.01;
+  at::Tensor gates = at::rand({T, R, 4 * H}, f32).to(at::kBFloat16);
+  at::Tensor c_all = at::randn({T, R, H}, f32);
+  at::Tensor dc = at::empty({R, H}, f32);
+  at::Tensor rng = at::zeros({2}, at::TensorOptions().dtype(at::kInt).device(dev));
+  BwdLoopArgs la{};
+  la.dG = reinterpret_cast<uint16_t*>(dG.data_ptr());
+  la.whhT = reinterpret_cast<const uint16_t*>(whhT.data_ptr());
+  la.dh = dh.data_ptr<float>();
+  la.gates = reinterpret_cast<const uint16_t*>(gates.data_ptr());
+  la.c_all = c_all.data_ptr<float>();
+  la.dc_out = dc.data_ptr<float>();
+  la.R = (int)R;
+  la.H = (int)H;
+  la.T = (int)T;
+  la.drop_p = 0.5f;
+  la.rng = reinterpret_cast<const uint32_t*>(rng.data_ptr());
+  la.cnt = loop_counters(dev.index(), lstm_bwd_loop_counter_ints((int)R, (int)H));
+  la.err = device_err_word(dev.index());
+  la.poll_bound = poll_bound();
+  la.dbg = (int)dbg;
+  la.form = dbg >= 8 ? 0 : 1;  // (dbg 8: the K-split form; 0-7: the row-read form's variants)
+  if (dbg >= 8) la.dbg = 0;
+  if (la.form == 0) la.xb = loop_xb(dev.index(), lstm_bwd_loop_xb_floats((int)R, (int)H));
+  hipStream_t st = cur_stream();
+  for (int i = 0; i < 3; ++i) launch_lstm_bwd_loop(la, st);
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0);
+  (void)hipEventCreate(&e1);
+  (void)hipEventRecord(e0, st);
+  for (int64_t i = 0; i < iters; ++i) launch_lstm_bwd_loop(la, st);
+  (void)hipEventRecord(e1, st);
+  if (phases.defined() && phases.numel() > 0) {
+    TORCH_CHECK(phases.scalar_type() == at::kLong && phases.is_cuda() && phases.is_contiguous(),
+                "phases: int64 GPU tensor");
+    la.phases = phases.data_ptr<int64_t>();
+    launch_lstm_bwd_loop(la, st);
+  }
+  (void)hipEventSynchronize(e1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  (void)hipStreamSynchronize(st);
+  return ms * 1e3 / std::max<int64_t>(iters, 1);
+}
+
+// test entry: C (M x N) fp32 = A[:K]^T B[:K]
+at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K) {
+  check_cuda(A, "A");
+  check_cuda(B, "B");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.stride(1) == 1 && B.stride(1) == 1 &&
+                  A.size(0) >= K && B.size(0) >= K && A.size(1) >= M && B.size(1) >= N,
+              "wgrad_tn: operand shapes");
+  at::Tensor C = at::empty({M, N}, A.options().dtype(at::kFloat));
+  TORCH_CHECK(wgrad_tn_into(A, A.stride(0), B, B.stride(0), M, N, K, C.data_ptr<float>(), N, M,
+                            nullptr, 0, cur_stream()),
+              "wgrad_tn: shapes not supported (N a multiple of 128, 16-byte rows)");
+  return C;
+}
+
+// test entry of the row-mapped store: row m of A[:K]^T B[:K] into row rmap[m]
+// of out (fp32, >= N columns, any row stride; rmap int32 (M), < 0 = dropped)
+void wgrad_tn_rows(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K, at::Tensor out,
+                   at::Tensor rmap) {
+  check_cuda(A, "A");
+  check_cuda(B, "B");
+  check_cuda(out, "out");
+  check_cuda(rmap, "rmap");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.stride(1) == 1 && B.stride(1) == 1 &&
+                  A.size(0) >= K && B.size(0) >= K && A.size(1) >= M && B.size(1) >= N,
+              "wgrad_tn_rows: operand shapes");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.stride(1) == 1 &&
+                  out.size(1) >= N && rmap.scalar_type() == at::kInt && rmap.is_contiguous() &&
+                  rmap.numel() == M,
+              "wgrad_tn_rows: out fp32 (rows, >= N), rmap int32 (M)");
+  TORCH_CHECK(rmap.max().item<int>() < out.size(0), "wgrad_tn_rows: rmap beyond the rows of out");
+  TORCH_CHECK(wgrad_tn_into(A, A.stride(0), B, B.stride(0), M, N, K, out.data_ptr<float>(),
+                            out.stride(0), M, nullptr, 0, cur_stream(), nullptr, nullptr,
+                            rmap.data_ptr<int>()),
+              "wgrad_tn_rows: shapes not supported (N a multiple of 128, 16-byte rows)");
+}
+
+// test entry of the fused form: {C (M x N), db (M)} with db[m] = sum_k al[k] A[k][m]
+std::vector<at::Tensor> wgrad_tn_colsum(at::Tensor A, at::Tensor B, at::Tensor al, int64_t M,
+                                        int64_t N, int64_t K) {
+  check_cuda(A, "A");
+  check_cuda(B, "B");
+  check_cuda(al, "al");
+  TORCH_CHECK(A.dim() == 2 && B.dim() == 2 && A.stride(1) == 1 && B.stride(1) == 1 &&
+                  A.size(0) >= K && B.size(0) >= K && A.size(1) >= M && B.size(1) >= N &&
+                  al.scalar_type() == at::kFloat && al.is_contiguous() && al.numel() >= K,
+              "wgrad_tn_colsum: operand shapes");
+  at::Tensor C = at::empty({M, N}, A.options().dtype(at::kFloat));
+  at::Tensor db = at::empty({M}, A.options().dtype(at::kFloat));
+  TORCH_CHECK(wgrad_tn_into(A, A.stride(0), B, B.stride(0), M, N, K, C.data_ptr<float>(), N, M,
+                            nullptr, 0, cur_stream(), al.data_ptr<float>(), db.data_ptr<float>()),
+              "wgrad_tn_colsum: shapes not supported (N = 512, 16-byte rows)");
+  return {C, db};
+}
+
+// stand-in for a collective's kernel on `stream` (0: the current stream):
+// `blocks` copying workgroups for `us` microseconds over `buf` (fp32 scratch)
+void busy_copy(at::Tensor buf, int64_t blocks, double us, int64_t stream) {
+  check_cuda(buf, "buf");
+  TORCH_CHECK(buf.scalar_type() == at::kFloat && buf.is_contiguous(), "busy_copy: fp32 scratch");
+  launch_busy_copy(buf.data_ptr<float>(), buf.numel(), (int)blocks, us,
+                   stream != 0 ? reinterpret_cast<hipStream_t>(stream) : cur_stream());
+}
+
+// Microbenchmarks of single kernels (scripts/microbench_kernels.py): mean
+// microseconds per launch over `iters` back-to-back launches, HIP events.
+template <class F>
+static double time_launches(F&& launch, int64_t iters, hipStream_t st) {
+  launch(0);
+  hipEvent_t e0, e1;
+  (void)hipEventCreate(&e0);
+  (void)hipEventCreate(&e1);
+  (void)hipEventRecord(e0, st);
+  for (int i = 0; i < iters; ++i) launch(i);
+  (void)hipEventRecord(e1, st);
+  (void)hipEventSynchronize(e1);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, e0, e1);
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  return 1000.0 * ms / (double)iters;
+}
+
+double vocab_fwd_bench(at::Tensor hd, at::Tensor wlog, at::Tensor blog, at::Tensor tgt,
+                       int64_t flags, bool save, int64_t iters, int64_t variant) {
+  const int64_t R = hd.size(0), H = hd.size(1), V = wlog.size(0);
+  TORCH_CHECK(H % 64 == 0 && wlog.size(1) == H && blog.numel() == V, "shapes");
+  auto dev = hd.device();
+  const int64_t ldl = (V + 7) / 8 * 8;
+  at::Tensor logits = save ? at::empty({R, ldl}, hd.options().dtype(at::kHalf)) : at::Tensor();
+  const int n_vt = vocab_num_tiles((int)V);
+  at::Tensor part = at::empty({(int64_t)n_vt * R * vocab_partial_bytes() / 4},
+                              at::TensorOptions().dtype(at::kFloat).device(dev));
+  at::Tensor rng = at::full({2}, 1234, at::TensorOptions().dtype(at::kInt).device(dev));
+  const int64_t* tg = tgt.defined() && tgt.numel() ? tgt.data_ptr<int64_t>() : nullptr;
+  hipStream_t st = cur_stream();
+  return time_launches(
+      [&](int i) {
+        launch_vocab_fwd_variant((int)variant, reinterpret_cast<const uint16_t*>(hd.data_ptr()),
+                                 (int)H, (int)R, (int)H,
+                                 reinterpret_cast<const uint16_t*>(wlog.data_ptr()),
+                                 blog.data_ptr<float>(), (int)V,
+                                 save ? reinterpret_cast<uint16_t*>(logits.data_ptr()) : nullptr,
+                                 ldl, part.data_ptr(), tg, 1, (int)flags, 1.f, rng_ptr(rng), i, st);
+      },
+      iters, st);
+}
+
+// bias-gradient column sums over the exp store: E (n, R, ldl) bf16, alpha (n*R)
+double vgrad_colsum_bench(at::Tensor E, at::Tensor alpha, int64_t V, int64_t iters) {
+  check_cuda(E, "E");
+  const int64_t NR = E.size(0) * E.size(1), ldl = E.size(2);
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(E.device());
+  at::Tensor part = at::empty({vgrad_colsum_blocks(NR), V}, f32), db = at::empty({V}, f32);
+  hipStream_t st = cur_stream();
+  return time_launches(
+      [&](int) {
+        launch_vgrad_colsum(reinterpret_cast<const uint16_t*>(E.data_ptr()), ldl, (int)V, NR,
+                            alpha.data_ptr<float>(), part.data_ptr<float>(), db.data_ptr<float>(),
+                            st);
+      },
+      iters, st);
+}
+
+// Phase stamps of one launch of the MFMA attention workgroups (microbenchmark,
+// scripts/microbench_att.py): (Bv * A / 64, 8) int64 wall-clock ticks, phases
+// 0 start, 1 operands in LDS, 2 query MFMA, 3 scores, 4 ticket, and for the
+// video's last workgroup 5 slot sums, 7 softmax, 6 end (-1 where not reached).
+at::Tensor att_mfma_phases(at::Tensor gv, at::Tensor P, at::Tensor wa, at::Tensor ba, int64_t R) {
+  check_cuda(gv, "gv");
+  const int64_t Bv = gv.size(0), C = gv.size(1), H4 = gv.size(2), A = P.size(2), H = H4 / 4;
+  const int vdiv = (int)(R / Bv), CP = C <= 8 ? 8 : 16;
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(gv.device());
+  auto bf = gv.options().dtype(at::kBFloat16);
+  at::Tensor h = (at::rand({R, H}, f32) * 2 - 1).to(at::kBFloat16);
+  at::Tensor wq = (at::randn({A, H}, f32) * 0.05).to(at::kBFloat16);
+  at::Tensor gv16 = at::zeros({Bv, H4, CP}, bf), vg = at::empty({R, H4}, bf);
+  gv16.narrow(2, 0, C).copy_(gv.transpose(1, 2));
+  at::Tensor alpha = at::empty({R, C}, f32), qo = at::empty({R, A}, f32);
+  at::Tensor ep = at::empty({Bv, A / 64, 32, CP}, f32);
+  at::Tensor cnt = at::zeros({Bv}, f32.dtype(at::kInt));
+  at::Tensor dbg = at::full({Bv * (A / 64), 8}, -1, f32.dtype(at::kLong));
+  AttMfmaArgs am{reinterpret_cast<const uint16_t*>(h.data_ptr()),
+                 reinterpret_cast<const uint16_t*>(wq.data_ptr()), P.data_ptr<float>(),
+                 wa.data_ptr<float>(), ba.data_ptr<float>(),
+                 reinterpret_cast<const uint16_t*>(gv16.data_ptr()), (int)H, (int)A, (int)C, CP,
+                 (int)H4, vdiv, (int)Bv, reinterpret_cast<uint16_t*>(vg.data_ptr()),
+                 alpha.data_ptr<float>(), qo.data_ptr<float>(), ep.data_ptr<float>(),
+                 cnt.data_ptr<int>(), nullptr, nullptr};
+  hipStream_t st = cur_stream();
+  launch_att_mfma_fwd(am, st);  // warm-up
+  (void)hipStreamSynchronize(st);
+  am.dbg = dbg.data_ptr<int64_t>();
+  launch_att_mfma_fwd(am, st);
+  (void)hipStreamSynchronize(st);
+  return dbg;
+}
+
+// temporal attention kernels alone (one decode / reverse step): Gv (Bv, C, 4H)
+// fp32, P (Bv, C, A), q (R, A), w_a (A), b_a (1); which = 0: forward
+// (accumulating into pre), 1: backward (dG rows (R, 4H + A) bf16, dq written)
+double att_bench(at::Tensor gv, at::Tensor P, at::Tensor q, at::Tensor wa, at::Tensor ba,
+                 int64_t R, int64_t which, int64_t iters) {
+  check_cuda(gv, "gv");
+  const int64_t Bv = gv.size(0), C = gv.size(1), H4 = gv.size(2), A = P.size(2);
+  TORCH_CHECK(R % Bv == 0 && q.size(0) == R && q.size(1) == A, "att_bench shapes");
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(gv.device());
+  const int vdiv = (int)(R / Bv);
+  at::Tensor pre = at::zeros({R, H4}, f32), alpha = at::full({R, C}, 1.f / C, f32);
+  at::Tensor dG = at::zeros({R, H4 + A}, gv.options().dtype(at::kBFloat16));
+  const int rpw_b = which == 4 ? 2 : ATT_BWD_RPW;  // 1: backward, 4: backward at 2 rows
+  const int64_t nwg = Bv * att_groups(vdiv, rpw_b);
+  at::Tensor dpp = at::zeros({nwg, C, A}, f32), dwp = at::zeros({nwg, A}, f32),
+             dbp = at::zeros({nwg, 1}, f32);
+  hipStream_t st = cur_stream();
+  const int64_t H = H4 / 4;
+  if (which == 5 || which == 6) {  // MFMA path: att_mfma forward workgroups / att_bwd_mfma
+    auto bf = gv.options().dtype(at::kBFloat16);
+    const int CP = C <= 8 ? 8 : 16;
+    at::Tensor h = (at::rand({R, H}, f32) * 2 - 1).to(at::kBFloat16);
+    at::Tensor wq = (at::randn({A, H}, f32) * 0.05).to(at::kBFloat16);
+    at::Tensor gv16 = at::zeros({Bv, H4, CP}, bf), vg = at::empty({R, H4}, bf);
+    gv16.narrow(2, 0, C).copy_(gv.transpose(1, 2));
+    at::Tensor qo = at::empty({R, A}, f32), dal = at::randn({H / 64, R, CP}, f32);
+    at::Tensor dP = at::zeros({Bv, C, A}, f32), dwa = at::zeros({Bv, A}, f32),
+               dba = at::zeros({Bv, 1}, f32);
+    at::Tensor ep = at::empty({Bv, A / 64, 32, CP}, f32);
+    at::Tensor cnt = at::zeros({Bv}, f32.dtype(at::kInt));
+    AttMfmaArgs am{reinterpret_cast<const uint16_t*>(h.data_ptr()),
+                   reinterpret_cast<const uint16_t*>(wq.data_ptr()), P.data_ptr<float>(),
+                   wa.data_ptr<float>(), ba.data_ptr<float>(),
+                   reinterpret_cast<const uint16_t*>(gv16.data_ptr()), (int)H, (int)A, (int)C, CP,
+                   (int)H4, vdiv, (int)Bv, reinterpret_cast<uint16_t*>(vg.data_ptr()),
+                   alpha.data_ptr<float>(), qo.data_ptr<float>(), ep.data_ptr<float>(),
+                   cnt.data_ptr<int>()};
+    return time_launches(
+        [&](int) {
+          if (which == 5)
+            launch_att_mfma_fwd(am, st);
+          else
+            launch_att_bwd_mfma(dal.data_ptr<float>(), (int)(H / 64), (int)R,
+                                alpha.data_ptr<float>(), q.data_ptr<float>(), P.data_ptr<float>(),
+                                wa.data_ptr<float>(), (int)Bv, vdiv, (int)C, CP, (int)A, (int)H4,
+                                reinterpret_cast<uint16_t*>(dG.data_ptr()), (int)(H4 + A), 1,
+                                dP.data_ptr<float>(), dwa.data_ptr<float>(),
+                                dba.data_ptr<float>(), st);
+        },
+        iters, st);
+  }
+  return time_launches(
+      [&](int) {
+        if (which != 1 && which != 4)  // forward at 4 (0), 2 (2) or 1 (3) rows per workgroup
+          launch_att_fwd(gv.data_ptr<float>(), P.data_ptr<float>(), q.data_ptr<float>(), nullptr,
+                         wa.data_ptr<float>(), ba.data_ptr<float>(), (int)Bv, vdiv, (int)C, (int)A,
+                         (int)H4, pre.data_ptr<float>(), alpha.data_ptr<float>(), st, 1, 0,
+                         which == 2 ? 2 : which == 3 ? 1 : 4);
+        else
+          launch_att_bwd(reinterpret_cast<uint16_t*>(dG.data_ptr()), (int)(H4 + A),
+                         gv.data_ptr<float>(), P.data_ptr<float>(), q.data_ptr<float>(),
+                         alpha.data_ptr<float>(), wa.data_ptr<float>(), (int)Bv, vdiv, (int)C,
+                         (int)A, (int)H4, 1, dpp.data_ptr<float>(), dwp.data_ptr<float>(),
+                         dbp.data_ptr<float>(), st, 0, rpw_b);
+      },
+      iters, st);
+}
+
+// counting sort of n token ids < V (the embedding-gradient grouping)
+double token_sort_bench(at::Tensor toks, int64_t V, int64_t iters) {
+  check_cuda(toks, "toks");
+  const int64_t N = toks.numel();
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(toks.device());
+  at::Tensor ws = at::empty({2 * V + 1}, i32), stok = at::empty({N}, i32), srow = at::empty({N}, i32);
+  hipStream_t st = cur_stream();
+  return time_launches(
+      [&](int) {
+        launch_token_sort(toks.data_ptr<int64_t>(), (int)N, (int)V, ws.data_ptr<int>(),
+                          stok.data_ptr<int>(), srow.data_ptr<int>(), st);
+      },
+      iters, st);
+}
+
+// the vocab projection + sampler/argmax + combine alone (tests of the exact
+// two-level sampler): rows hd (R, H) bf16 -> {token (R) int64, lse (R)}.
+// mode: SEL_SAMPLE_H (1) or SEL_GREEDY_H (2).
+// MFMA temporal-attention workgroups as a launch of their own (tests /
+// microbenchmarks of kernels/att_mfma.h): h (R, H) bf16, wq (A, H) bf16,
+// P (Bv, C, A), wa (A), ba (1) fp32, gv (Bv, C, 4H) fp32 ->
+// {vg (R, 4H) bf16, alpha (R, C), q (R, A)}
+std::vector<at::Tensor> att_mfma_fwd(at::Tensor h, at::Tensor wq, at::Tensor P, at::Tensor wa,
+                                     at::Tensor ba, at::Tensor gv, int64_t whole) {
+  for (auto* t : {&h, &wq, &P, &wa, &ba, &gv}) check_cuda(*t, "att_mfma operand");
+  TORCH_CHECK(h.scalar_type() == at::kBFloat16 && wq.scalar_type() == at::kBFloat16 &&
+                  P.scalar_type() == at::kFloat && wa.scalar_type() == at::kFloat &&
+                  ba.scalar_type() == at::kFloat && gv.scalar_type() == at::kFloat,
+              "att_mfma: h / wq bf16, P / wa / ba / gv fp32");
+  const int64_t R = h.size(0), H = h.size(1), A = wq.size(0), Bv = P.size(0), C = P.size(1);
+  TORCH_CHECK(wq.size(1) == H && P.size(2) == A && wa.numel() == A && ba.numel() == 1 &&
+                  gv.size(0) == Bv && gv.size(1) == C && gv.size(2) == 4 * H && R % Bv == 0,
+              "att_mfma: operand shapes");
+  const int vdiv = (int)(R / Bv), CP = C <= 8 ? 8 : 16;
+  TORCH_CHECK(att_mfma_fwd_ok(vdiv, (int)C, (int)A, (int)H, 0), "att_mfma: unsupported shape");
+  at::Tensor gv16 = at::zeros({Bv, 4 * H, CP}, h.options());
+  gv16.narrow(2, 0, C).copy_(gv.transpose(1, 2));
+  at::Tensor vg = at::empty({R, 4 * H}, h.options());
+  at::Tensor alpha = at::empty({R, C}, P.options()), q = at::empty({R, A}, P.options());
+  at::Tensor ep = at::empty({Bv, A / 64, 32, CP}, P.options());
+  at::Tensor cnt = at::zeros({Bv}, P.options().dtype(at::kInt));
+  AttMfmaArgs a{reinterpret_cast<const uint16_t*>(h.data_ptr()),
+                reinterpret_cast<const uint16_t*>(wq.data_ptr()), P.data_ptr<float>(),
+                wa.data_ptr<float>(), ba.data_ptr<float>(),
+                reinterpret_cast<const uint16_t*>(gv16.data_ptr()), (int)H, (int)A, (int)C, CP,
+                (int)(4 * H), vdiv, (int)Bv, reinterpret_cast<uint16_t*>(vg.data_ptr()),
+                alpha.data_ptr<float>(), q.data_ptr<float>(), ep.data_ptr<float>(),
+                cnt.data_ptr<int>()};
+  a.whole = whole < 0 ? att_mfma_whole_default((int)C, (int)H) : (whole != 0 ? 1 : 0);
+  launch_att_mfma_fwd(a, cur_stream());
+  return {vg, alpha, q};
+}
+
+std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor blog,
+                                     at::Tensor rng, int64_t mode, double temperature,
+                                     int64_t step) {
+  check_cuda(hd, "hd");
+  check_cuda(wlog, "wlog");
+  TORCH_CHECK(hd.scalar_type() == at::kBFloat16 && wlog.scalar_type() == at::kBFloat16 &&
+                  blog.scalar_type() == at::kFloat, "bf16 hd / W, fp32 bias");
+  TORCH_CHECK(mode == SEL_SAMPLE_H || mode == SEL_GREEDY_H, "mode: 1 sample, 2 greedy");
+  const int64_t R = hd.size(0), H = hd.size(1), V = wlog.size(0);
+  TORCH_CHECK(H % 64 == 0 && wlog.size(1) == H && blog.numel() == V, "shapes");
+  auto dev = hd.device();
+  const int n_vt = vocab_num_tiles((int)V);
+  at::Tensor part = at::empty({(int64_t)n_vt * R * vocab_partial_bytes() / 4},
+                              at::TensorOptions().dtype(at::kFloat).device(dev));
+  at::Tensor tok = at::zeros({R, 1}, at::TensorOptions().dtype(at::kLong).device(dev));
+  at::Tensor lse = at::empty({R}, at::TensorOptions().dtype(at::kFloat).device(dev));
+  hipStream_t st = cur_stream();
+  launch_vocab_fwd(reinterpret_cast<const uint16_t*>(hd.data_ptr()), (int)H, (int)R, (int)H,
+                   reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(),
+                   (int)V, nullptr, 0, part.data_ptr(), nullptr, 0, mode == SEL_SAMPLE_H ? 1 : 2,
+                   (float)(1.0 / temperature), rng_ptr(rng), (int)step, st);
+  launch_vocab_combine(part.data_ptr(), n_vt, (int)R, lse.data_ptr<float>(),
+                       tok.data_ptr<int64_t>(), 1, nullptr, 0, nullptr, 0, nullptr, 0, (int)mode,
+                       0.f, rng_ptr(rng), (int)step, nullptr, 0, nullptr, st);
+  return {tok.view({R}), lse};
+}
+
+// One decode step for tests: the decode launch + vocab_combine_kernel.  save: 0 none, 1 fp16 logits, 2 exp store
+// (eoff given).  Cell (ptab defined): the next step's cell from c_prev and
+// the chosen tokens (dropout drop_p, step key `step + 1`).  eos: 0 no
+// end-of-sequence rules; 1 / 2 the all-rows-ended counter with a live / dead
+// previous step; unfinished (R) uint8 nullable: the per-row mask, updated in
+// place.  Returns {lse, tok, g_sel, g_xe, saved rows (R, ldl), pre (R, 4H),
+// n_parts, h, c, h_drop, gates, counts}.
+std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor wlog,
+                                         at::Tensor blog, at::Tensor whh, at::Tensor vgate,
+                                         int64_t vdiv, at::Tensor tgt, at::Tensor eoff,
+                                         int64_t save, int64_t mode, int64_t step, at::Tensor rng,
+                                         at::Tensor ptab, at::Tensor c_prev, double drop_p,
+                                         int64_t cell, int64_t eos, at::Tensor unfinished,
+                                         double ss_prob) {
+  check_cuda(hd, "hd");
+  check_cuda(wlog, "wlog");
+  const int64_t R = hd.size(0), H = hd.size(1), V = wlog.size(0);
+  TORCH_CHECK(hd.scalar_type() == at::kBFloat16 && wlog.scalar_type() == at::kBFloat16 &&
+                  hd.is_contiguous() && wlog.is_contiguous() && wlog.size(1) == H &&
+                  blog.scalar_type() == at::kFloat && blog.numel() == V, "hd / wlog / blog");
+  const bool lstm = whh.defined() && whh.numel() > 0;
+  if (lstm)
+    TORCH_CHECK(h.scalar_type() == at::kBFloat16 && h.is_contiguous() && h.sizes() == hd.sizes() &&
+                    whh.scalar_type() == at::kBFloat16 && whh.is_contiguous() &&
+                    whh.size(0) == 4 * H && whh.size(1) == H, "h / whh");
+  const bool has_vg = vgate.defined() && vgate.numel() > 0;
+  if (has_vg)
+    TORCH_CHECK(vgate.scalar_type() == at::kFloat && vgate.is_contiguous() &&
+                    vgate.size(0) * vdiv == R && vgate.size(1) == 4 * H, "vgate (R / vdiv, 4H)");
+  const bool has_tgt = tgt.defined() && tgt.numel() > 0;
+  if (has_tgt) TORCH_CHECK(tgt.scalar_type() == at::kLong && tgt.numel() == R, "tgt (R) int64");
+  if (save == 2)
+    TORCH_CHECK(eoff.defined() && eoff.scalar_type() == at::kFloat && eoff.numel() == R, "eoff (R)");
+  const bool do_cell = ptab.defined() && ptab.numel() > 0;
+  if (do_cell) {
+    TORCH_CHECK(lstm, "the cell needs the recurrent part");
+    check_cuda(ptab, "ptab");
+    check_cuda(c_prev, "c_prev");
+    TORCH_CHECK(ptab.scalar_type() == at::kHalf && ptab.size(0) == V && ptab.size(1) == 4 * H &&
+                    c_prev.scalar_type() == at::kFloat && c_prev.numel() == R * H,
+                "ptab (V, 4H) fp16 / c_prev (R, H) fp32");
+  }
+  const bool has_unf = unfinished.defined() && unfinished.numel() > 0;
+  if (has_unf)
+    TORCH_CHECK(unfinished.is_cuda() && unfinished.scalar_type() == at::kByte &&
+                    unfinished.numel() == R, "unfinished (R) uint8");
+  auto dev = hd.device();
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+  auto bf = at::TensorOptions().dtype(at::kBFloat16).device(dev);
+  const int64_t ldl = (V + 63) / 64 * 64;
+  at::Tensor part = at::empty({(int64_t)vocab_part_slots((int)V) * R * vocab_partial_bytes() / 4}, f32);
+  at::Tensor saved = save ? at::zeros({R, ldl}, at::TensorOptions()
+                                                    .dtype(save == 2 ? at::kBFloat16 : at::kHalf)
+                                                    .device(dev))
+                          : at::Tensor();
+  at::Tensor pre = lstm ? at::zeros({R, 4 * H}, f32) : at::Tensor();
+  at::Tensor lse = at::empty({R}, f32), gsel = at::zeros({R}, f32), gxe = at::zeros({R}, f32);
+  at::Tensor tok = at::zeros({R}, at::TensorOptions().dtype(at::kLong).device(dev));
+  at::Tensor h_out, c_out, hdrop, gates;
+  if (do_cell) {
+    h_out = at::zeros({R, H}, bf);
+    c_out = at::zeros({R, H}, f32);
+    hdrop = at::zeros({R, H}, bf);
+    gates = at::zeros({R, 4 * H}, bf);
+  }
+  // counts: steps 0..2 of the end-of-sequence flags; this step is count step 2
+  const int cps = combine_count_ints_per_step();
+  at::Tensor counts = at::zeros({3 * cps}, at::TensorOptions().dtype(at::kInt).device(dev));
+  if (eos == 1) counts.narrow(0, cps, 1).fill_(1);  // a live row at the previous step
+  int* CNT = eos ? counts.data_ptr<int>() : nullptr;
+  hipStream_t st = cur_stream();
+  const int flags = (mode == SEL_SAMPLE_H || mode == SEL_SS_H ? 1 : 0) |
+                    (mode == SEL_GREEDY_H ? 2 : 0) | (save == 2 ? 16 : 0);
+  const int64_t* TG = has_tgt ? tgt.data_ptr<int64_t>() : nullptr;
+  uint8_t* UNF = has_unf ? unfinished.data_ptr<uint8_t>() : nullptr;
+  const int n = launch_vocab_lstm_fwd(
+      reinterpret_cast<const uint16_t*>(hd.data_ptr()), (int)H, (int)R, (int)H,
+      reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(), (int)V,
+      save ? reinterpret_cast<uint16_t*>(saved.data_ptr()) : nullptr, ldl, part.data_ptr(), TG, 1,
+      flags, 1.f, rng_ptr(rng), (int)step,
+      lstm ? reinterpret_cast<const uint16_t*>(h.data_ptr()) : nullptr,
+      lstm ? reinterpret_cast<const uint16_t*>(whh.data_ptr()) : nullptr,
+      has_vg ? vgate.data_ptr<float>() : nullptr, (int)vdiv, lstm ? pre.data_ptr<float>() : nullptr,
+      st, 0, nullptr, save == 2 ? eoff.data_ptr<float>() : nullptr, nullptr);
+  CellLaunch cl{};
+  if (do_cell)
+    cl = CellLaunch{pre.data_ptr<float>(), reinterpret_cast<const uint16_t*>(ptab.data_ptr()),
+                    c_prev.data_ptr<float>(), c_out.data_ptr<float>(),
+                    reinterpret_cast<uint16_t*>(h_out.data_ptr()),
+                    reinterpret_cast<uint16_t*>(hdrop.data_ptr()), (int)H,
+                    reinterpret_cast<uint16_t*>(gates.data_ptr()), (int)H, (float)drop_p,
+                    (int)step + 1, (int)cell, nullptr, 0};
+  launch_vocab_combine(part.data_ptr(), n, (int)R, lse.data_ptr<float>(), tok.data_ptr<int64_t>(),
+                       1, gsel.data_ptr<float>(), 1, has_tgt ? gxe.data_ptr<float>() : nullptr, 1,
+                       TG, 1, (int)mode, (float)ss_prob, rng_ptr(rng), (int)step, CNT, 2, UNF, st,
+                       do_cell ? &cl : nullptr);
+  return {lse, tok, gsel, gxe, saved, pre, at::full({1}, n, at::TensorOptions().dtype(at::kLong)),
+          h_out, c_out, hdrop, gates, counts};
+}
+
+// the counting sort itself, for tests: returns {stok, srow} (int32)
+std::vector<at::Tensor> token_sort(at::Tensor toks, int64_t V) {
+  check_cuda(toks, "toks");
+  TORCH_CHECK(toks.scalar_type() == at::kLong, "int64 token ids");
+  const int64_t N = toks.numel();
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(toks.device());
+  at::Tensor ws = at::empty({2 * V + 1}, i32), stok = at::empty({N}, i32), srow = at::empty({N}, i32);
+  launch_token_sort(toks.data_ptr<int64_t>(), (int)N, (int)V, ws.data_ptr<int>(),
+                    stok.data_ptr<int>(), srow.data_ptr<int>(), cur_stream());
+  return {stok, srow};
+}
+
+// per-token row sums for tests: x (N, C) bf16, toks (N) int64 -> S (V, C) bf16
+at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V) {
+  check_cuda(x, "x");
+  check_cuda(toks, "toks");
+  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1, "x: (N, C) bf16");
+  TORCH_CHECK(toks.scalar_type() == at::kLong && toks.numel() == x.size(0), "toks: (N) int64");
+  const int64_t N = toks.numel(), C = x.size(1);
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(toks.device());
+  at::Tensor ws = at::empty({2 * V + 1}, i32), stok = at::empty({N}, i32), srow = at::empty({N}, i32);
+  at::Tensor S = at::empty({V, C}, x.options());
+  at::Tensor S64 = at::empty({V, C}, x.options().dtype(at::kDouble));
+  hipStream_t st = cur_stream();
+  launch_token_sort(toks.data_ptr<int64_t>(), (int)N, (int)V, ws.data_ptr<int>(),
+                    stok.data_ptr<int>(), srow.data_ptr<int>(), st);
+  launch_token_long_zero(ws.data_ptr<int>(), (int)V, (int)C, S64.data_ptr<double>(), st);
+  launch_token_group_sum(reinterpret_cast<const uint16_t*>(x.data_ptr()), (int)C, x.stride(0),
+                         stok.data_ptr<int>(), srow.data_ptr<int>(), (int)N, ws.data_ptr<int>(),
+                         (int)V, reinterpret_cast<uint16_t*>(S.data_ptr()), S64.data_ptr<double>(),
+                         st);
+  return S;
+}
+
+}  // namespace cst

@@ -100,7 +100,7 @@ __device__ __forceinline__ void lstm_gemm_block(int bid, const uint16_t* __restr
 }
 
 // The whole LSTM step of one tile (recurrent GEMM + the cell), for the XE
-// all-rows forward (engine.cpp): with teacher forcing the input token of step
+// all-rows forward (decoder_forward.cpp): with teacher forcing the input token of step
 // t+1 is its label, known before the vocabulary projection of step t, so the
 // cell needs no combine and the step rides in the decode launch of the
 // previous step's vocabulary tiles.  gates = h_t W_hh^T + vgate + P[tok] ->

@@ -817,7 +817,7 @@ __global__ __launch_bounds__(256, OCC) void vocab_lstm_fwd_kernel(
   vocab_tr_block<BN, STAGES, TOPK>(bid - n_lstm_pad, lds, VOCAB_TR_ARGS);
 }
 
-// XE all rows (engine.cpp): the first n_lstm_pad workgroups run the WHOLE
+// XE all rows (decoder_forward.cpp): the first n_lstm_pad workgroups run the WHOLE
 // LSTM step of the next rows (lstm_gemm.h lstm_cell_block: the input token is
 // the label, so the cell needs no combine), the rest the vocabulary tiles of
 // the current rows.  Either part may be empty.

@@ -21,7 +21,7 @@
 // 2^-10 (|a| + |b|) s: its softmax part is then off by at most 2^-10 (|a| +
 // |b|) in total.
 //
-// (The XE all-rows forward, engine.cpp, writes E = exp(x) with c = 0 for every
+// (The XE all-rows forward, decoder_forward.cpp, writes E = exp(x) with c = 0 for every
 // row: VGradRows::zero_off, s_r = exp(-lse_r), guarded for |lse_r| > 60.)
 //
 // Range of the exp store: E = exp(x - c) with c = the previous step's LSE

@@ -235,7 +235,7 @@ void launch_vocab_exp_convert(uint16_t* buf, int64_t ldl, int V, int R, const fl
 // vocab_grad.hip: vocab-head backward from the exp store (see that file).
 // Row weights of the NR = n_steps * R rollout rows: sampled / chosen tokens
 // (weight dg_sel) and XE targets (weight dg_xe)
-// XE all rows (engine.cpp): the cell operands of a whole-step LSTM tile
+// XE all rows (decoder_forward.cpp): the cell operands of a whole-step LSTM tile
 // (lstm_gemm.h lstm_cell_block) inside the previous step's decode launch
 struct XeCell {
   const int64_t* tok;  // input tokens of the step (row stride tok_stride)
@@ -273,7 +273,7 @@ struct VGradRows {
   // EXP_SAFE_LSE_JUMP from the previous step are listed here by
   // vgrad_onehot ([0] = count, then flat row ids) and recomputed by vgrad_fix
   int* fix;
-  // forward-computed X = E W (engine.cpp "X in the rollout"): vgrad_onehot also
+  // forward-computed X = E W (decoder_backward.cpp have_x, "X in the rollout"): vgrad_onehot also
   // writes each row's one-hot weights / tokens (nullable outputs, NR each;
   // token -1 = none), so the loop forms dHd = alpha X + a W[ys] + b W[yx]
   // without the folded E', and vgrad_fix recomputes the listed rows of X

@@ -1,0 +1,441 @@
+// Around the decoder: FeatPool, the losses, the metric scorers, the flat Adam step.
+#include "engine_internal.h"
+
+namespace cst {
+
+// FeatPool (csrc/kernels/featpool.hip): xs[f] (rows, d_f), ws[f] (H, d_f),
+// bs[f] (H), all fp32 contiguous GPU tensors; returns the concatenated
+// (rows, F*H) output after ReLU and dropout (mask from rng slot 0).
+// idx (optional, int64 (n)): xs are then the resident tables (table rows * C,
+// d_f) and the call covers the rows idx[r / C] * C + r % C, r < n * C.
+static FeatPoolArgs featpool_args(const std::vector<at::Tensor>& xs,
+                                  const std::vector<at::Tensor>& ws,
+                                  const std::vector<at::Tensor>& bs,
+                                  const c10::optional<at::Tensor>& idx = c10::nullopt,
+                                  int64_t C = 1) {
+  TORCH_CHECK(!xs.empty() && xs.size() <= FEATPOOL_MAX_F && ws.size() == xs.size() &&
+                  (bs.empty() || bs.size() == xs.size()),
+              "featpool: 1..", FEATPOOL_MAX_F, " modalities, one weight (and bias) each");
+  FeatPoolArgs a{};
+  a.nf = (int)xs.size();
+  a.rows = (int)xs[0].size(0);
+  a.H = (int)ws[0].size(0);
+  const int64_t x_rows = xs[0].size(0);
+  if (idx.has_value() && idx->defined()) {
+    check_cuda(*idx, "featpool idx");
+    TORCH_CHECK(idx->scalar_type() == at::kLong && idx->dim() == 1 && idx->is_contiguous() &&
+                    idx->numel() > 0 && C >= 1 && x_rows > 0 && x_rows % C == 0 &&
+                    idx->numel() * C < (1LL << 31) && idx->device() == xs[0].device(),
+                "featpool: idx int64 (n) on the features' device, tables of (table rows * C) rows");
+    a.idx = idx->data_ptr<int64_t>();
+    a.C = (int)C;
+    a.n_table = (int)(x_rows / C);
+    a.rows = (int)(idx->numel() * C);
+  }
+  TORCH_CHECK(a.H % 64 == 0, "featpool: output size must be a multiple of 64");
+  for (int f = 0; f < a.nf; ++f) {
+    const at::Tensor &x = xs[f], &w = ws[f];
+    // x may be a column slice of a wider row (the loader gathers every
+    // modality in one pass): unit column stride, 16-byte-aligned rows
+    TORCH_CHECK(x.is_cuda(), "featpool x must be a GPU tensor");
+    check_cuda(w, "featpool w");
+    TORCH_CHECK(x.scalar_type() == at::kFloat && w.scalar_type() == at::kFloat && x.dim() == 2 &&
+                    w.dim() == 2 && x.size(0) == x_rows && w.size(0) == a.H &&
+                    x.size(1) == w.size(1) && x.size(1) % 4 == 0 &&
+                    (x.size(1) == 1 || x.stride(1) == 1) && x.stride(0) % 4 == 0 &&
+                    x.stride(0) >= x.size(1) &&
+                    reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+                "featpool: fp32 x (rows, d) with unit column stride and 16-byte-aligned rows, "
+                "w (H, d), d % 4 == 0");
+    a.s[f].x = x.data_ptr<float>();
+    a.s[f].w = w.data_ptr<float>();
+    if (!bs.empty()) {
+      check_cuda(bs[f], "featpool b");
+      TORCH_CHECK(bs[f].scalar_type() == at::kFloat && bs[f].numel() == a.H, "featpool: bias (H)");
+      a.s[f].b = bs[f].data_ptr<float>();
+    }
+    a.s[f].d = (int)x.size(1);
+    a.s[f].ld = (int)x.stride(0);
+  }
+  featpool_layout(a);
+  return a;
+}
+
+at::Tensor featpool_forward(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
+                            std::vector<at::Tensor> bs, double drop_p, at::Tensor rng,
+                            c10::optional<at::Tensor> idx, int64_t C) {
+  TORCH_CHECK(bs.size() == xs.size(), "featpool: one bias per modality");
+  FeatPoolArgs a = featpool_args(xs, ws, bs, idx, C);
+  auto f32 = xs[0].options();
+  at::Tensor wsp = at::empty({(int64_t)a.fwd_blocks * 64 * 64}, f32);
+  at::Tensor out = at::empty({a.rows, (int64_t)a.nf * a.H}, f32);
+  launch_featpool_fwd(a, wsp.data_ptr<float>(), out.data_ptr<float>(), nullptr, (float)drop_p,
+                      rng_ptr(rng), cur_stream());
+  return out;
+}
+
+// {out fp32 (rows, F*H), out as bf16 (round to nearest even)}: FeatPool for
+// the gate GEMM that follows (bf16 operand, no conversion pass)
+std::vector<at::Tensor> featpool_forward16(std::vector<at::Tensor> xs, std::vector<at::Tensor> ws,
+                                           std::vector<at::Tensor> bs, double drop_p,
+                                           at::Tensor rng, c10::optional<at::Tensor> idx,
+                                           int64_t C) {
+  TORCH_CHECK(bs.size() == xs.size(), "featpool: one bias per modality");
+  FeatPoolArgs a = featpool_args(xs, ws, bs, idx, C);
+  auto f32 = xs[0].options();
+  at::Tensor wsp = at::empty({(int64_t)a.fwd_blocks * 64 * 64}, f32);
+  at::Tensor out = at::empty({a.rows, (int64_t)a.nf * a.H}, f32);
+  at::Tensor out16 = at::empty({a.rows, (int64_t)a.nf * a.H}, f32.dtype(at::kBFloat16));
+  launch_featpool_fwd(a, wsp.data_ptr<float>(), out.data_ptr<float>(),
+                      reinterpret_cast<uint16_t*>(out16.data_ptr()), (float)drop_p, rng_ptr(rng),
+                      cur_stream());
+  return {out, out16};
+}
+
+// -> {dW_0 .. dW_{F-1}, db_0 .. db_{F-1}} given dL/d(out) and the forward's out;
+// written into `outs` (2F contiguous fp32 tensors, e.g. gradient-bucket
+// slots) when given
+std::vector<at::Tensor> featpool_backward(at::Tensor dout, at::Tensor out,
+                                          std::vector<at::Tensor> xs,
+                                          std::vector<at::Tensor> ws, double drop_p,
+                                          std::vector<at::Tensor> outs,
+                                          c10::optional<at::Tensor> idx, int64_t C) {
+  FeatPoolArgs a = featpool_args(xs, ws, {}, idx, C);
+  check_cuda(dout, "featpool dout");
+  check_cuda(out, "featpool out");
+  TORCH_CHECK(dout.scalar_type() == at::kFloat && out.scalar_type() == at::kFloat &&
+                  dout.numel() == (int64_t)a.rows * a.nf * a.H && out.numel() == dout.numel(),
+              "featpool: dout / out (rows, F*H) fp32");
+  std::vector<at::Tensor> res;
+  FeatPoolGrads g{};
+  if (!outs.empty()) {
+    TORCH_CHECK((int)outs.size() == 2 * a.nf, "featpool: outs = {dW_f} + {db_f}");
+    for (int f = 0; f < a.nf; ++f) {
+      TORCH_CHECK(outs[f].is_cuda() && outs[f].is_contiguous() &&
+                      outs[f].scalar_type() == at::kFloat && outs[f].numel() == ws[f].numel() &&
+                      outs[a.nf + f].is_cuda() && outs[a.nf + f].is_contiguous() &&
+                      outs[a.nf + f].scalar_type() == at::kFloat && outs[a.nf + f].numel() == a.H,
+                  "featpool: output slots must be contiguous fp32 (H, d) / (H)");
+    }
+    res = outs;
+  } else {
+    for (int f = 0; f < a.nf; ++f) res.push_back(at::empty_like(ws[f]));
+    for (int f = 0; f < a.nf; ++f) res.push_back(at::empty({a.H}, ws[f].options()));
+  }
+  for (int f = 0; f < a.nf; ++f) {
+    g.dw[f] = res[f].data_ptr<float>();
+    g.db[f] = res[a.nf + f].data_ptr<float>();
+  }
+  launch_featpool_bwd(a, dout.data_ptr<float>(), out.data_ptr<float>(), (float)drop_p, g,
+                      cur_stream());
+  return res;
+}
+
+// SCST loss (csrc/kernels/loss.hip): seq (R, T) int64, lp (R, T) fp32,
+// sample (R), greedy (R or R / gdiv) fp32 -> {loss (0-dim), out = [loss, m, b,
+// sum mask], reward (R)}
+std::vector<at::Tensor> scst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor sample,
+                                          at::Tensor greedy) {
+  for (auto* t : {&seq, &lp, &sample, &greedy}) check_cuda(*t, "scst_loss operand");
+  const int64_t R = seq.size(0), T = seq.size(1);
+  TORCH_CHECK(seq.scalar_type() == at::kLong && lp.scalar_type() == at::kFloat &&
+                  lp.size(0) == R && lp.size(1) == T && sample.scalar_type() == at::kFloat &&
+                  sample.numel() == R && greedy.scalar_type() == at::kFloat &&
+                  greedy.numel() > 0 && R % greedy.numel() == 0,
+              "scst_loss: seq / lp (R, T), sample (R), greedy (R or R / rows per video)");
+  auto f32 = lp.options();
+  at::Tensor out = at::empty({4}, f32), reward = at::empty({R}, f32), loss = at::empty({}, f32);
+  at::Tensor ws = at::zeros({scst_loss_ws_ints((int)R)}, f32.dtype(at::kInt));
+  launch_scst_loss_fwd(seq.data_ptr<int64_t>(), lp.data_ptr<float>(), (int)R, (int)T,
+                       sample.data_ptr<float>(), greedy.data_ptr<float>(),
+                       (int)(R / greedy.numel()), reward.data_ptr<float>(), out.data_ptr<float>(),
+                       loss.data_ptr<float>(), ws.data_ptr<int>(), CstBase{nullptr, 0, 0},
+                       cur_stream());
+  return {loss, out, reward};
+}
+
+// CST loss (the same launch, consensus baseline): scores (R) fp32 of the
+// rewarded rows, S rows per video (R % S == 0, S <= 64); bref: (R) GT
+// consensus scores (scb_baseline 1) or empty (scb_baseline 2: the scores
+// themselves); k = scb_captions (0: reward = score) -> {loss, out, reward}
+std::vector<at::Tensor> cst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor scores,
+                                         at::Tensor bref, int64_t S, int64_t k) {
+  for (auto* t : {&seq, &lp, &scores}) check_cuda(*t, "cst_loss operand");
+  const int64_t R = seq.size(0), T = seq.size(1);
+  const bool has_ref = bref.defined() && bref.numel() > 0;
+  TORCH_CHECK(seq.scalar_type() == at::kLong && lp.scalar_type() == at::kFloat &&
+                  lp.size(0) == R && lp.size(1) == T && scores.scalar_type() == at::kFloat &&
+                  scores.numel() == R && S >= 1 && S <= 64 && R % S == 0 && k >= 0 && k <= S,
+              "cst_loss: seq / lp (R, T), scores (R), 1 <= S <= 64 dividing R, 0 <= k <= S");
+  if (has_ref) {
+    check_cuda(bref, "cst_loss bref");
+    TORCH_CHECK(bref.scalar_type() == at::kFloat && bref.numel() == R, "cst_loss: bref (R) fp32");
+  }
+  auto f32 = lp.options();
+  at::Tensor out = at::empty({4}, f32), reward = at::empty({R}, f32), loss = at::empty({}, f32);
+  at::Tensor ws = at::zeros({scst_loss_ws_ints((int)R)}, f32.dtype(at::kInt));
+  launch_scst_loss_fwd(seq.data_ptr<int64_t>(), lp.data_ptr<float>(), (int)R, (int)T,
+                       scores.data_ptr<float>(), scores.data_ptr<float>(), 1,
+                       reward.data_ptr<float>(), out.data_ptr<float>(), loss.data_ptr<float>(),
+                       ws.data_ptr<int>(),
+                       CstBase{has_ref ? bref.data_ptr<float>() : nullptr, (int)S, (int)k},
+                       cur_stream());
+  return {loss, out, reward};
+}
+
+at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
+                              at::Tensor dloss) {
+  for (auto* t : {&seq, &reward, &out, &dloss}) check_cuda(*t, "scst_loss operand");
+  TORCH_CHECK(dloss.scalar_type() == at::kFloat && dloss.numel() == 1, "dloss: fp32 scalar");
+  const int64_t R = seq.size(0), T = seq.size(1);
+  at::Tensor dlp = at::empty({R, T}, reward.options());
+  launch_scst_loss_bwd(seq.data_ptr<int64_t>(), reward.data_ptr<float>(), out.data_ptr<float>(),
+                       dloss.data_ptr<float>(), (int)R, (int)T, dlp.data_ptr<float>(),
+                       cur_stream());
+  return dlp;
+}
+
+// XE loss (csrc/kernels/loss.hip): labels (R, L) int64 -- the full label
+// rows the loader's masks come from --, lp (R, T) fp32 gathered GT log-probs
+// of columns off .. off + T - 1 -> {loss (0-dim), out = [loss, sum mask], cnt
+// (R) counted positions per row}
+std::vector<at::Tensor> xe_loss_forward(at::Tensor labels, at::Tensor lp, int64_t off) {
+  check_cuda(labels, "xe_loss labels");
+  check_cuda(lp, "xe_loss lp");
+  const int64_t R = labels.size(0), L = labels.size(1), T = lp.size(1);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && lp.scalar_type() == at::kFloat &&
+                  labels.dim() == 2 && lp.dim() == 2 && lp.size(0) == R && off >= 0 &&
+                  off + T <= L,
+              "xe_loss: labels (R, L) int64, lp (R, T) fp32 with off + T <= L");
+  auto f32 = lp.options();
+  at::Tensor out = at::empty({2}, f32), cnt = at::empty({R}, f32), loss = at::empty({}, f32);
+  at::Tensor ws = at::zeros({scst_loss_ws_ints((int)R)}, f32.dtype(at::kInt));
+  launch_xe_loss_fwd(labels.data_ptr<int64_t>(), (int)L, (int)off, lp.data_ptr<float>(), (int)R,
+                     (int)T, cnt.data_ptr<float>(), out.data_ptr<float>(), loss.data_ptr<float>(),
+                     ws.data_ptr<int>(), cur_stream());
+  return {loss, out, cnt};
+}
+
+at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, int64_t T) {
+  for (auto* t : {&cnt, &out, &dloss}) check_cuda(*t, "xe_loss operand");
+  TORCH_CHECK(dloss.scalar_type() == at::kFloat && dloss.numel() == 1 &&
+                  cnt.scalar_type() == at::kFloat && out.numel() == 2,
+              "xe_loss_backward: fp32 cnt (R), out (2), dloss scalar");
+  const int64_t R = cnt.size(0);
+  at::Tensor dlp = at::empty({R, T}, cnt.options());
+  launch_xe_loss_bwd(cnt.data_ptr<float>(), out.data_ptr<float>(), dloss.data_ptr<float>(), (int)R,
+                     (int)T, dlp.data_ptr<float>(), cur_stream());
+  return dlp;
+}
+
+// On-GPU CIDEr-D scores of N hypotheses.
+at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
+                       double log_ref_len, int64_t use_eos, bool clipped) {
+  check_cuda(hyps, "hyps");
+  check_cuda(hyp_video, "hyp_video");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
+              "int64 inputs");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  // (clipped = false: coco CIDEr of the validation scorer, up to 64 tokens)
+  TORCH_CHECK(T <= (clipped ? 63 : 64), "hypotheses longer than ", clipped ? 63 : 64,
+              " tokens are not supported");
+  at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
+  (clipped ? launch_cider_d : launch_cider_unclipped)(
+      hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N,
+                 t["ht_keys"].data_ptr<int64_t>(), t["ht_vals"].data_ptr<float>(),
+                 (uint32_t)t["ht_keys"].numel(), t["vid_ref_off"].data_ptr<int32_t>(),
+                 t["ref_ng_off"].data_ptr<int32_t>(), t["ref_norm"].data_ptr<float>(),
+                 t["ref_len"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
+                 t["ng_val"].data_ptr<float>(), (float)log_ref_len, (int)use_eos, out.data_ptr<float>(),
+                 cur_stream());
+  return out;
+}
+
+// On-GPU sentence BLEU-4 / ROUGE-L scores of N hypotheses (kernels/sent_metrics.hip).
+// No allocation besides the result and no synchronisation: capturable.
+at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
+                        std::map<std::string, at::Tensor> t, int64_t use_eos) {
+  check_cuda(hyps, "hyps");
+  check_cuda(hyp_video, "hyp_video");
+  TORCH_CHECK(hyps.dim() == 2 && hyp_video.dim() == 1 && hyp_video.size(0) == hyps.size(0),
+              "hyps (N, T) and hyp_video (N)");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
+              "int64 inputs");
+  const bool bleu = metric == "Bleu_4";
+  TORCH_CHECK(bleu || metric == "ROUGE_L", "metric_score: metric must be Bleu_4 or ROUGE_L, got ",
+              metric);
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  TORCH_CHECK(T <= 64, "hypotheses of ", T, " tokens; at most 64 are supported");
+  for (const char* k : {"vid_ref_off", "ref_len", "vid_ng_off", "ng_key", "ng_cnt", "ref_tok_off",
+                        "ref_tok"}) {
+    TORCH_CHECK(t.count(k), "metric tables lack ", k);
+    check_cuda(t[k], k);
+    TORCH_CHECK(t[k].scalar_type() == (std::string(k) == "ng_key" ? at::kLong : at::kInt),
+                "metric table ", k, " has the wrong dtype");
+  }
+  const int Nv = (int)t["vid_ref_off"].numel() - 1;
+  TORCH_CHECK(Nv >= 0 && t["vid_ng_off"].numel() == Nv + 1 &&
+                  t["ref_tok_off"].numel() == t["ref_len"].numel() + 1,
+              "metric tables are inconsistent");
+  at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
+  if (bleu)
+    launch_bleu4(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                 t["vid_ref_off"].data_ptr<int32_t>(), t["ref_len"].data_ptr<int32_t>(),
+                 t["vid_ng_off"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
+                 t["ng_cnt"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
+                 cur_stream());
+  else
+    launch_rouge_l(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                   t["vid_ref_off"].data_ptr<int32_t>(), t["ref_tok_off"].data_ptr<int32_t>(),
+                   t["ref_tok"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
+                   cur_stream());
+  return out;
+}
+
+// Validation scorer (kernels/corpus_metrics.hip): per-hypothesis statistics of
+// corpus BLEU ((N, 10) int32) or METEOR ((N, 6) int32 and the (N) fp64 segment
+// scores) against the tables of metric_build_tables (METEOR: built with stem
+// ids, which are passed again for the hypothesis tokens).
+static int check_corpus_inputs(at::Tensor& hyps, at::Tensor& hyp_video,
+                               std::map<std::string, at::Tensor>& t,
+                               std::initializer_list<const char*> keys) {
+  check_cuda(hyps, "hyps");
+  check_cuda(hyp_video, "hyp_video");
+  TORCH_CHECK(hyps.dim() == 2 && hyp_video.dim() == 1 && hyp_video.size(0) == hyps.size(0),
+              "hyps (N, T) and hyp_video (N)");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong &&
+                  hyps.is_contiguous() && hyp_video.is_contiguous(),
+              "contiguous int64 inputs");
+  TORCH_CHECK(hyps.size(1) <= 64, "hypotheses of ", hyps.size(1),
+              " tokens; at most 64 are supported");
+  for (const char* k : keys) {
+    TORCH_CHECK(t.count(k), "metric tables lack ", k);
+    check_cuda(t[k], k);
+    TORCH_CHECK(t[k].scalar_type() == (std::string(k) == "ng_key" ? at::kLong : at::kInt) &&
+                    t[k].is_contiguous(),
+                "metric table ", k, " has the wrong dtype or layout");
+  }
+  const int Nv = (int)t["vid_ref_off"].numel() - 1;
+  TORCH_CHECK(Nv >= 0, "metric tables are inconsistent");
+  return Nv;
+}
+
+at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t) {
+  const int Nv = check_corpus_inputs(hyps, hyp_video, t,
+                                     {"vid_ref_off", "ref_len", "vid_ng_off", "ng_key", "ng_cnt"});
+  TORCH_CHECK(t["vid_ng_off"].numel() == Nv + 1 && t["ng_cnt"].numel() == t["ng_key"].numel(),
+              "metric tables are inconsistent");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  at::Tensor out = at::empty({N, 10}, hyps.options().dtype(at::kInt));
+  launch_bleu_stats(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                    t["vid_ref_off"].data_ptr<int32_t>(), t["ref_len"].data_ptr<int32_t>(),
+                    t["vid_ng_off"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
+                    t["ng_cnt"].data_ptr<int32_t>(), out.data_ptr<int32_t>(), cur_stream());
+  return out;
+}
+
+std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
+                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids) {
+  const int Nv = check_corpus_inputs(hyps, hyp_video, t,
+                                     {"vid_ref_off", "ref_len", "ref_tok_off", "ref_tok",
+                                      "ref_stem"});
+  check_cuda(stem_ids, "stem_ids");
+  TORCH_CHECK(stem_ids.scalar_type() == at::kInt && stem_ids.dim() == 1 &&
+                  stem_ids.is_contiguous(),
+              "stem_ids: contiguous int32 (V)");
+  TORCH_CHECK(t["ref_tok_off"].numel() == t["ref_len"].numel() + 1 &&
+                  t["ref_stem"].numel() == t["ref_tok"].numel(),
+              "metric tables are inconsistent (built without stem ids?)");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  at::Tensor stats = at::empty({N, 6}, hyps.options().dtype(at::kInt));
+  at::Tensor score = at::empty({N}, hyps.options().dtype(at::kDouble));
+  launch_meteor_stats(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
+                      t["vid_ref_off"].data_ptr<int32_t>(), t["ref_tok_off"].data_ptr<int32_t>(),
+                      t["ref_tok"].data_ptr<int32_t>(), t["ref_stem"].data_ptr<int32_t>(),
+                      stem_ids.data_ptr<int32_t>(), (int)stem_ids.numel(),
+                      stats.data_ptr<int32_t>(), score.data_ptr<double>(), cur_stream());
+  return {stats, score};
+}
+
+// Shadow-copy segments from Python: meta = int64 CPU (n, 8) rows {off, n,
+// kind, cols, H, E, ld2, slots}; dsts = 2 tensors per row (dst, dst2; undefined or
+// empty when unused).
+static ShadowSegs make_shadow_segs(const at::Tensor& meta, const std::vector<at::Tensor>& dsts) {
+  ShadowSegs ss{};
+  if (!meta.defined() || meta.numel() == 0) return ss;
+  TORCH_CHECK(!meta.is_cuda() && meta.scalar_type() == at::kLong && meta.dim() == 2 &&
+                  meta.size(1) == 8 && meta.size(0) <= SHADOW_MAX_SEGS,
+              "shadow meta must be an int64 CPU (n <= ", SHADOW_MAX_SEGS, ", 8) tensor");
+  TORCH_CHECK((int64_t)dsts.size() == 2 * meta.size(0), "two destination tensors per segment");
+  auto m = meta.accessor<int64_t, 2>();
+  ss.n = (int)meta.size(0);
+  for (int k = 0; k < ss.n; ++k) {
+    ShadowSeg& g = ss.s[k];
+    g.off = m[k][0], g.n = m[k][1], g.kind = (int)m[k][2], g.cols = (int)m[k][3];
+    g.H = (int)m[k][4], g.E = (int)m[k][5], g.ld2 = (int)m[k][6], g.slots = (int)m[k][7];
+    const at::Tensor& d = dsts[2 * k];
+    const at::Tensor& d2 = dsts[2 * k + 1];
+    TORCH_CHECK(d.is_cuda() && d.scalar_type() == at::kBFloat16, "shadow dst must be bf16 GPU");
+    g.dst = reinterpret_cast<uint16_t*>(d.data_ptr());
+    g.dst2 = d2.defined() && d2.numel() ? reinterpret_cast<uint16_t*>(d2.data_ptr()) : nullptr;
+    if (g.kind == SHADOW_PLAIN) {
+      TORCH_CHECK(d.numel() >= g.n, "plain shadow too small");
+    } else {
+      const int64_t rows = g.cols > 0 ? g.n / g.cols : 0;
+      const int64_t gates = g.H > 0 ? rows / g.H : 0;
+      TORCH_CHECK(g.H > 0 && g.cols > 0 && g.n % g.cols == 0 && rows % g.H == 0 &&
+                      (gates == 1 || gates == 3 || gates == 4) &&
+                      d.numel() >= 4 * (int64_t)g.H * (g.E + g.H),
+                  "gate-weight shadow segment shape");
+      for (int q = 0; q < gates; ++q)
+        for (int q2 = 0; q2 < q; ++q2)
+          TORCH_CHECK(((g.slots >> (2 * q)) & 3) != ((g.slots >> (2 * q2)) & 3),
+                      "gate slot map must be injective");
+      if (g.kind == SHADOW_GATES_HH)
+        TORCH_CHECK(g.dst2 != nullptr && g.cols == g.H && d2.numel() >= 4 * (int64_t)g.H * g.ld2,
+                    "W_hh shadow needs its packed copy");
+      if (g.kind == SHADOW_GATES_IH && g.dst2 != nullptr)
+        TORCH_CHECK(g.cols > g.E && g.ld2 >= g.cols - g.E && d2.numel() >= 4 * (int64_t)g.H * g.ld2,
+                    "W_ih video-column shadow shape");
+    }
+  }
+  return ss;
+}
+
+// hyper (device fp32): [lr, step before, skipped, step after] (kernels/adam.hip).
+// phase: 0 = both passes; 1 = sum of squares only (the caller all-reduces the
+// partials of a sharded update before phase 2); 2 = update only.
+at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
+                          at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
+                          double b1, double b2, double eps, double clip, double gscale,
+                          int64_t phase, at::Tensor shadow_meta,
+                          std::vector<at::Tensor> shadow_dst) {
+  check_cuda(p, "p");
+  for (auto* t : {&g, &m, &v}) {
+    check_cuda(*t, "adam operand");
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->numel() == p.numel(), "adam operand shape");
+  }
+  TORCH_CHECK(partials.numel() >= 1024 && scal.numel() >= 2, "workspace too small");
+  TORCH_CHECK(hyper.is_cuda() && hyper.scalar_type() == at::kFloat && hyper.numel() >= 4,
+              "hyper must be fp32 [lr, step, skipped, step after] on the GPU");
+  TORCH_CHECK(phase >= 0 && phase <= 2, "phase: 0 both, 1 sumsq, 2 update");
+  const ShadowSegs ss = make_shadow_segs(shadow_meta, shadow_dst);
+  for (int k = 0; k < ss.n; ++k)
+    TORCH_CHECK(ss.s[k].off >= 0 && ss.s[k].off + ss.s[k].n <= p.numel(), "shadow range");
+  launch_flat_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
+                   v.data_ptr<float>(), p.numel(), partials.data_ptr<float>(),
+                   skip.data_ptr<bool>(), scal.data_ptr<float>(), hyper.data_ptr<float>(),
+                   (float)b1, (float)b2, (float)eps, (float)clip, (float)gscale, (int)phase, ss,
+                   cur_stream());
+  return scal.narrow(0, 0, 1).squeeze(0);
+}
+
+void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tensor> shadow_dst) {
+  check_cuda(p, "p");
+  const ShadowSegs ss = make_shadow_segs(shadow_meta, shadow_dst);
+  for (int k = 0; k < ss.n; ++k)
+    TORCH_CHECK(ss.s[k].off >= 0 && ss.s[k].off + ss.s[k].n <= p.numel(), "shadow range");
+  launch_shadow_refresh(p.data_ptr<float>(), ss, cur_stream());
+}
+
+}  // namespace cst

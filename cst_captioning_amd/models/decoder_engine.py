@@ -1,6 +1,7 @@
 """Fused HIP decoder engine (MI355X path of :class:`CaptionModel`).
 
-Wraps the C++ executor of ``csrc/engine.cpp`` (time loops) and the gfx950
+Wraps the C++ executor of ``csrc/decoder_forward.cpp``, ``decoder_backward.cpp`` and
+``beam_search.cpp`` (time loops; shared state in ``csrc/engine.cpp``) and the gfx950
 kernels of ``csrc/kernels`` in one autograd Function, so a whole
 rollout / teacher-forced pass is ONE node of the autograd graph:
 
@@ -81,7 +82,7 @@ from ..utils.consts import const_tensor
 from ..utils.text import BOS
 
 SEL_GT, SEL_SAMPLE, SEL_GREEDY, SEL_SS = 0, 1, 2, 3
-# teacher-forced training forwards on the XE decode launches (csrc/engine.cpp
+# teacher-forced training forwards on the XE decode launches (csrc/decoder_forward.cpp
 # "XE all rows"); CSTCAP_XE_ROWS=0: the general per-step launches + combine
 XE_ROWS = os.environ.get('CSTCAP_XE_ROWS', '1') != '0'
 
@@ -175,7 +176,7 @@ class _DecoderFn(torch.autograd.Function):
         if h0 is not None:  # bf16 h (the recurrent GEMM operand), fp32 c
             state0 = [h0.detach().bfloat16().contiguous(), c0.detach().float().contiguous()]
         store_exp = bool(save and not want_full)
-        # XE all rows (csrc/engine.cpp): teacher forcing of a training forward
+        # XE all rows (csrc/decoder_forward.cpp): teacher forcing of a training forward
         # runs one launch per step (vocabulary tiles of step t + the whole LSTM
         # step t+1) with the combines on a side stream
         xe_rows = bool(store_exp and want_xe and labels is not None and not has_att
@@ -630,7 +631,7 @@ class DecoderEngine:
 
     def launch_x(self, stream=None):
         """X = E W of the last training forward (the vocab head's backward GEMM
-        without the one-hot terms; see csrc/engine.cpp "X in the rollout") on
+        without the one-hot terms; see csrc/decoder_backward.cpp have_x) on
         ``stream``, after the rollout: the GEMM then runs while the rewards
         and the loss are computed, and the backward's reverse loop reads
         alpha X + the one-hot rows instead of waiting for the GEMM.  No-op

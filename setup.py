@@ -77,10 +77,13 @@ class BuildWithHip(BuildExtension):
 # dependency), unlike ASan, which the host-only tests cover
 # (tests/test_native_sanitizers.py).
 SANITIZE = os.environ.get('CSTCAP_HOST_SANITIZE') == '1'
+# every host unit (paths relative to this file, as setuptools wants them)
+HOST_SOURCES = sorted(os.path.relpath(p, HERE).replace(os.sep, '/')
+                      for pat in ('*.cpp', os.path.join('host', '*.cpp'))
+                      for p in glob.glob(os.path.join(HERE, 'csrc', pat)))
 ext = CppExtension(
     'cst_captioning_amd._C_san' if SANITIZE else 'cst_captioning_amd._C',
-    ['csrc/engine.cpp', 'csrc/bindings.cpp', 'csrc/host/cider_host.cpp',
-     'csrc/host/metric_host.cpp', 'csrc/host/blaslt_tuned.cpp'],
+    HOST_SOURCES,
     include_dirs=[os.path.join(HERE, 'csrc')] + include_paths(device_type='cuda'),
     define_macros=[('__HIP_PLATFORM_AMD__', '1'), ('USE_ROCM', '1')]
     + ([('_GLIBCXX_ASSERTIONS', '1')] if SANITIZE else []),

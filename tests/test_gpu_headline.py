@@ -278,7 +278,7 @@ def test_headline_beam5_graph_replay_equals_eager():
 
 @pytest.mark.parametrize('bias_shift', [0.0, 70.0])
 def test_headline_teacher_forced_xe_launches_match_per_step(bias_shift):
-    """XE all rows (csrc/engine.cpp: one launch per step = the vocabulary tiles
+    """XE all rows (csrc/decoder_forward.cpp: one launch per step = the vocabulary tiles
     of step t + the whole LSTM step t+1, E = exp(x) with offset 0, the combines
     on a side stream) against the general per-step launches + combine (E =
     exp(x - previous LSE)): the same target log-probs and parameter

@@ -9,6 +9,7 @@ Every test here runs the native extension on the GPU (``pytest -m gpu``):
   * the reference's "all rows emitted EOS" stop rule on the device.
 """
 import copy
+import os
 
 import numpy as np
 import pytest
@@ -52,6 +53,18 @@ def test_extension_loaded_from_tree():
     import cst_captioning_amd
     m = _ext()
     assert cst_captioning_amd.__path__[0] in m.__file__
+
+
+def test_extension_entry_points_unchanged():
+    """The extension binds exactly the names recorded in
+    tests/golden/ext_entry_points.txt (one per line): no binding is lost or
+    renamed when the host sources are reorganised."""
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden',
+                          'ext_entry_points.txt')
+    with open(golden) as f:
+        want = {line.strip() for line in f if line.strip()}
+    got = {n for n in dir(_ext()) if not n.startswith('_')}
+    assert got == want, (sorted(got - want), sorted(want - got))
 
 
 def test_cider_kernel_matches_oracle():
@@ -638,7 +651,7 @@ def test_exp_store_lse_jump_rows_recomputed():
                                 [], empty, empty, 0, [], [], empty, empty, 1, empty, [], 0, 0.0)
     bad = res0[1]
     assert (not torch.isfinite(bad).all()) or (bad - ref_w).norm() / ref_w.norm() > 0.1
-    # X = E W from the rollout (engine.cpp "X in the rollout"): the listed rows'
+    # X = E W from the rollout (decoder_backward.cpp have_x, "X in the rollout"): the listed rows'
     # X is recomputed from their exact E, the loop adds the one-hot rows, and
     # every gradient equals the X-less path's
     xw = (Es_fresh[:, :, :V].float() @ wlog.float()).contiguous()  # inf / nan rows included
