@@ -68,6 +68,11 @@ SCB_BASELINE?=1
 USE_RL?=0
 USE_RL_AFTER?=0
 USE_EOS?=0
+# GT consensus scores: file = prepro/evalscores.py on the coco-format strings,
+# read by --train_bcmrscores_pkl; tokens = scored in token space from the label
+# table (compute_evalscores writes the same file layout; train computes them at
+# start-up and reads no file)
+CONSENSUS_SCORER?=file
 USE_MIXER?=0
 MIXER_FROM?=-1
 SS_K?=100
@@ -138,8 +143,18 @@ compute_ciderdf: $(foreach s,$(SPLITS),$(patsubst %,$(META_DIR)/%_$(s)_ciderdf.p
 	$(PREPRO).ciderdf $^ $@ --output_words --vocab_json $(firstword $(subst _, ,$@))_train_vocab.json
 
 compute_evalscores: $(patsubst %,$(META_DIR)/$(TRAIN_DATASET)_%_evalscores.pkl,$(SPLITS))
+ifeq ($(CONSENSUS_SCORER),tokens)
+EVALSCORES_OPT=--scorer tokens --label_file $*_sequencelabel.$(LABEL_EXT) \
+	--cached_tokens $(META_DIR)/$(TRAIN_DATASET)_train_ciderdf.pkl --use_eos $(USE_EOS)
+BCMR_DEP=
+BCMR_OPT=--consensus_scorer tokens
+else
+EVALSCORES_OPT=
+BCMR_DEP=$(META_DIR)/$(TRAIN_DATASET)_$(TRAIN_SPLIT)_evalscores.pkl
+BCMR_OPT=--train_bcmrscores_pkl $(word 7,$^)
+endif
 %_evalscores.pkl: %_cocofmt.json
-	$(PREPRO).evalscores $^ $@ --seq_per_img $(TRAIN_SEQ_PER_IMG) --remove_in_ref
+	$(PREPRO).evalscores $^ $@ --seq_per_img $(TRAIN_SEQ_PER_IMG) --remove_in_ref $(EVALSCORES_OPT)
 
 #####################################################################################################################
 noop=
@@ -169,7 +184,7 @@ $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth: \
 	$(META_DIR)/$(TRAIN_DATASET)_$(TRAIN_SPLIT)_cocofmt.json \
 	$(META_DIR)/$(VAL_DATASET)_$(VAL_SPLIT)_cocofmt.json \
 	$(META_DIR)/$(TEST_DATASET)_$(TEST_SPLIT)_cocofmt.json \
-	$(META_DIR)/$(TRAIN_DATASET)_$(TRAIN_SPLIT)_evalscores.pkl \
+	$(BCMR_DEP) \
 	$(patsubst %,$(FEAT_DIR)/$(TRAIN_DATASET)_$(TRAIN_SPLIT)_%_mp$(NUM_CHUNKS).$(FEAT_EXT),$(FEATS)) \
 	$(patsubst %,$(FEAT_DIR)/$(VAL_DATASET)_$(VAL_SPLIT)_%_mp$(NUM_CHUNKS).$(FEAT_EXT),$(FEATS)) \
 	$(patsubst %,$(FEAT_DIR)/$(TEST_DATASET)_$(TEST_SPLIT)_%_mp$(NUM_CHUNKS).$(FEAT_EXT),$(FEATS))
@@ -181,7 +196,7 @@ $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth: \
 		--train_cocofmt_file $(word 4,$^) \
 		--val_cocofmt_file $(word 5,$^) \
 		--test_cocofmt_file $(word 6,$^) \
-		--train_bcmrscores_pkl $(word 7,$^) \
+		$(BCMR_OPT) \
 		--train_feat_h5 $(patsubst %,$(FEAT_DIR)/$(TRAIN_DATASET)_$(TRAIN_SPLIT)_%_mp$(NUM_CHUNKS).$(FEAT_EXT),$(FEATS)) \
 		--val_feat_h5 $(patsubst %,$(FEAT_DIR)/$(VAL_DATASET)_$(VAL_SPLIT)_%_mp$(NUM_CHUNKS).$(FEAT_EXT),$(FEATS)) \
 		--test_feat_h5 $(patsubst %,$(FEAT_DIR)/$(TEST_DATASET)_$(TEST_SPLIT)_%_mp$(NUM_CHUNKS).$(FEAT_EXT),$(FEATS)) \

@@ -49,11 +49,25 @@ static void cpu_hyps(at::Tensor& hyps, at::Tensor& hyp_video) {
   hyp_video = hyp_video.contiguous().to(at::kLong);
 }
 
+// the CPU scorers' optional leave-one-out array: (N) as contiguous int64 (`keep`
+// owns the converted copy), null when not given
+static const int64_t* cpu_exclude(const c10::optional<at::Tensor>& exclude, int64_t N,
+                                  at::Tensor& keep) {
+  if (!exclude.has_value() || !exclude->defined()) return nullptr;
+  TORCH_CHECK(!exclude->is_cuda() && exclude->dim() == 1 && exclude->size(0) == N,
+              "exclude: CPU (N)");
+  keep = exclude->contiguous().to(at::kLong);
+  return keep.data_ptr<int64_t>();
+}
+
 static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                   std::map<std::string, at::Tensor> t, double log_ref_len,
-                                  int64_t use_eos, bool clipped) {
+                                  int64_t use_eos, bool clipped,
+                                  c10::optional<at::Tensor> exclude) {
   hyps = hyps.contiguous().to(at::kLong);
   hyp_video = hyp_video.contiguous().to(at::kLong);
+  at::Tensor ex_keep;
+  const int64_t* ex = cpu_exclude(exclude, hyps.size(0), ex_keep);
   CiderTablesView v{(uint32_t)t["ht_keys"].numel(), t["ht_keys"].data_ptr<int64_t>(),
                     t["ht_vals"].data_ptr<float>(), t["vid_ref_off"].data_ptr<int32_t>(),
                     t["ref_ng_off"].data_ptr<int32_t>(), t["ref_norm"].data_ptr<float>(),
@@ -62,7 +76,7 @@ static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
   at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
   cider_score_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
                    hyp_video.data_ptr<int64_t>(), v, log_ref_len, (int)use_eos,
-                   out.data_ptr<float>(), clipped);
+                   out.data_ptr<float>(), clipped, ex);
   return out;
 }
 
@@ -93,6 +107,8 @@ static std::map<std::string, at::Tensor> metric_build_tables(
       {"vid_ng_off", to_tensor(t.vid_ng_off, at::kInt)},
       {"ng_key", to_tensor(t.ng_key, at::kLong)},
       {"ng_cnt", to_tensor(t.ng_cnt, at::kInt)},
+      {"ng_cnt2", to_tensor(t.ng_cnt2, at::kInt)},
+      {"ng_arg", to_tensor(t.ng_arg, at::kInt)},
       {"ref_tok_off", to_tensor(t.ref_tok_off, at::kInt)},
       {"ref_tok", to_tensor(t.ref_tok, at::kInt)}};
   if (stems.defined())  // (validation scorer: the references' stem rows as well)
@@ -101,24 +117,33 @@ static std::map<std::string, at::Tensor> metric_build_tables(
 }
 
 static MetricTablesView metric_view(std::map<std::string, at::Tensor>& t) {
-  return {(int)t.at("vid_ref_off").numel() - 1,
-          t.at("vid_ref_off").data_ptr<int32_t>(), t.at("ref_len").data_ptr<int32_t>(),
-          t.at("vid_ng_off").data_ptr<int32_t>(), t.at("ng_key").data_ptr<int64_t>(),
-          t.at("ng_cnt").data_ptr<int32_t>(), t.at("ref_tok_off").data_ptr<int32_t>(),
-          t.at("ref_tok").data_ptr<int32_t>()};
+  MetricTablesView v{(int)t.at("vid_ref_off").numel() - 1,
+                     t.at("vid_ref_off").data_ptr<int32_t>(), t.at("ref_len").data_ptr<int32_t>(),
+                     t.at("vid_ng_off").data_ptr<int32_t>(), t.at("ng_key").data_ptr<int64_t>(),
+                     t.at("ng_cnt").data_ptr<int32_t>(), t.at("ref_tok_off").data_ptr<int32_t>(),
+                     t.at("ref_tok").data_ptr<int32_t>()};
+  if (t.count("ng_cnt2") && t.count("ng_arg") &&
+      t.at("ng_cnt2").numel() == t.at("ng_key").numel() &&
+      t.at("ng_arg").numel() == t.at("ng_key").numel()) {
+    v.ng_cnt2 = t.at("ng_cnt2").data_ptr<int32_t>();
+    v.ng_arg = t.at("ng_arg").data_ptr<int32_t>();
+  }
+  return v;
 }
 
 static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
                                    at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                                   int64_t use_eos) {
+                                   int64_t use_eos, c10::optional<at::Tensor> exclude) {
   const bool bleu = metric == "Bleu_4";
   TORCH_CHECK(bleu || metric == "ROUGE_L", "metric_score_cpu: metric must be Bleu_4 or ROUGE_L, got ",
               metric);
   cpu_hyps(hyps, hyp_video);
+  at::Tensor ex_keep;
+  const int64_t* ex = cpu_exclude(exclude, hyps.size(0), ex_keep);
   at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
   (bleu ? bleu4_score_host : rouge_l_score_host)(
       hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
-      hyp_video.data_ptr<int64_t>(), metric_view(t), (int)use_eos, out.data_ptr<float>());
+      hyp_video.data_ptr<int64_t>(), metric_view(t), (int)use_eos, out.data_ptr<float>(), ex);
   return out;
 }
 
@@ -134,8 +159,11 @@ static at::Tensor bleu_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
 
 static std::vector<at::Tensor> meteor_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                                 std::map<std::string, at::Tensor> t,
-                                                at::Tensor stem_ids) {
+                                                at::Tensor stem_ids,
+                                                c10::optional<at::Tensor> exclude) {
   cpu_hyps(hyps, hyp_video);
+  at::Tensor ex_keep;
+  const int64_t* ex = cpu_exclude(exclude, hyps.size(0), ex_keep);
   TORCH_CHECK(t.count("ref_stem") && t.at("ref_stem").numel() == t.at("ref_tok").numel(),
               "metric tables were built without stem ids");
   stem_ids = stem_ids.contiguous().to(at::kInt);
@@ -144,7 +172,8 @@ static std::vector<at::Tensor> meteor_stats_cpu(at::Tensor hyps, at::Tensor hyp_
   meteor_stats_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1),
                     hyp_video.data_ptr<int64_t>(), metric_view(t),
                     t.at("ref_stem").data_ptr<int32_t>(), stem_ids.data_ptr<int32_t>(),
-                    (int)stem_ids.numel(), stats.data_ptr<int32_t>(), score.data_ptr<double>());
+                    (int)stem_ids.numel(), stats.data_ptr<int32_t>(), score.data_ptr<double>(),
+                    ex);
   return {stats, score};
 }
 }  // namespace cst
@@ -164,12 +193,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vg_idx") = py::none(), py::arg("vg_C") = 1);
   m.def("cider_build_tables", &cst::cider_build_tables);
   // clipped = false: coco CIDEr (no clipping, no length penalty), the validation metric
+  // exclude (here and in the metric scorers below): optional (N) int64, the
+  // in-video index of a reference each hypothesis leaves out (leave-one-out
+  // scoring of GT captions, ops/consensus.py); negative entries leave none out
   m.def("cider_score", &cst::cider_score, py::arg("hyps"), py::arg("hyp_video"),
         py::arg("tables"), py::arg("log_ref_len"), py::arg("use_eos"),
-        py::arg("clipped") = true);
+        py::arg("clipped") = true, py::arg("exclude") = py::none());
   m.def("cider_score_cpu", &cst::cider_score_cpu, py::arg("hyps"), py::arg("hyp_video"),
         py::arg("tables"), py::arg("log_ref_len"), py::arg("use_eos"),
-        py::arg("clipped") = true);
+        py::arg("clipped") = true, py::arg("exclude") = py::none());
   m.def("metric_build_tables", &cst::metric_build_tables, py::arg("labels"), py::arg("start"),
         py::arg("end"), py::arg("use_eos"), py::arg("stem_ids") = py::none(),
         "sentence BLEU-4 / ROUGE-L reference tables of a dataset (dict of CPU tensors); with "
@@ -179,15 +211,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bleu_stats_cpu", &cst::bleu_stats_cpu, py::arg("hyps"), py::arg("hyp_video"),
         py::arg("tables"));
   m.def("meteor_stats", &cst::meteor_stats, py::arg("hyps"), py::arg("hyp_video"),
-        py::arg("tables"), py::arg("stem_ids"),
+        py::arg("tables"), py::arg("stem_ids"), py::arg("exclude") = py::none(),
         "METEOR alignment statistics per hypothesis on the GPU: (N, 6) int32, (N) fp64");
   m.def("meteor_stats_cpu", &cst::meteor_stats_cpu, py::arg("hyps"), py::arg("hyp_video"),
-        py::arg("tables"), py::arg("stem_ids"));
+        py::arg("tables"), py::arg("stem_ids"), py::arg("exclude") = py::none());
   m.def("metric_score", &cst::metric_score, py::arg("metric"), py::arg("hyps"),
         py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
-        "Bleu_4 | ROUGE_L sentence scores on the GPU (one launch, capturable)");
+        py::arg("exclude") = py::none(), "Bleu_4 | ROUGE_L sentence scores on the GPU (one launch, capturable)");
   m.def("metric_score_cpu", &cst::metric_score_cpu, py::arg("metric"), py::arg("hyps"),
-        py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"));
+        py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
+        py::arg("exclude") = py::none());
   m.def("flat_adam_step", &cst::flat_adam_step);
   m.def("refresh_shadows", &cst::refresh_shadows);
   m.def("vocab_fwd_bench", &cst::vocab_fwd_bench);

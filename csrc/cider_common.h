@@ -40,6 +40,18 @@ CST_HD float df_lookup(const int64_t* keys, const float* vals, uint32_t cap, uin
   return 0.f;
 }
 
+// Leave-one-out scoring (GT consensus scores): exclude[hyp] = e leaves out
+// reference e of the hypothesis' video, counted from the start of the video's
+// range [r0, r1) of vid_ref_off.  Returns the absolute index of the reference to
+// skip, or -1 for none: a null array, e < 0, e >= the number of references, or a
+// video with a single reference (which is then kept:
+// prepro/evalscores.py `rest if rest else refs[v]`).
+CST_HD int excluded_ref(const int64_t* exclude, int hyp, int r0, int r1) {
+  if (!exclude) return -1;
+  const int64_t e = exclude[hyp];
+  return (e >= 0 && e < (int64_t)(r1 - r0) && r1 - r0 > 1) ? r0 + (int)e : -1;
+}
+
 #if defined(__HIPCC__)
 // Hypothesis compaction shared by the reward kernels (cider_d.hip,
 // sent_metrics.hip), run by ONE whole wavefront on row `row` of (., T <= 64)

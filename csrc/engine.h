@@ -90,12 +90,15 @@ at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, in
 at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
                               at::Tensor dloss);
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                       double log_ref_len, int64_t use_eos, bool clipped);
+                       double log_ref_len, int64_t use_eos, bool clipped,
+                       c10::optional<at::Tensor> exclude);
 at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t);
 std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
-                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids);
+                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids,
+                                     c10::optional<at::Tensor> exclude);
 at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
-                        std::map<std::string, at::Tensor> t, int64_t use_eos);
+                        std::map<std::string, at::Tensor> t, int64_t use_eos,
+                        c10::optional<at::Tensor> exclude);
 at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                           at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
                           double b1, double b2, double eps, double clip, double gscale,

@@ -95,7 +95,7 @@ CiderTables build_cider_tables(const int64_t* labels, int M, int L, const int64_
 
 void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                       const CiderTablesView& t, double log_ref_len, int use_eos,
-                      float* out, bool clipped) {
+                      float* out, bool clipped, const int64_t* exclude) {
   std::vector<int> toks;
   std::vector<std::pair<uint64_t, int>> grams;
   for (int i = 0; i < N; ++i) {
@@ -113,8 +113,10 @@ void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
     const double lh = std::max((int)toks.size() - 1, 0);
     const int v = (int)hyp_video[i];
     const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
+    const int ex = excluded_ref(exclude, i, r0, r1);
     double total = 0;
     for (int r = r0; r < r1; ++r) {
+      if (r == ex) continue;
       double acc[4] = {0, 0, 0, 0};
       for (int g = t.ref_ng_off[r]; g < t.ref_ng_off[r + 1]; ++g) {
         auto it = vh.find((uint64_t)t.ng_key[g]);
@@ -133,7 +135,8 @@ void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
         total += val * pen;
       }
     }
-    out[i] = (r1 > r0) ? (float)(10.0 * total / (4.0 * (r1 - r0))) : 0.f;
+    const int nref = r1 - r0 - (ex >= 0 ? 1 : 0);
+    out[i] = (nref > 0) ? (float)(10.0 * total / (4.0 * nref)) : 0.f;
   }
 }
 

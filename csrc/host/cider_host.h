@@ -33,8 +33,11 @@ CiderTables build_cider_tables(const int64_t* labels, int M, int L, const int64_
                                const int64_t* end, int Nv, const int64_t* df_keys,
                                const float* df_vals, int n_df, double log_ref_len, int use_eos);
 
+// exclude (N, optional): leave-one-out scoring, exclude[i] = the in-video index
+// of a reference that hypothesis i does not see (excluded_ref, cider_common.h);
+// the mean is over the references used.
 void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                       const CiderTablesView& t, double log_ref_len, int use_eos, float* out,
-                      bool clipped = true);
+                      bool clipped = true, const int64_t* exclude = nullptr);
 
 }  // namespace cst

@@ -4,8 +4,9 @@
 //  * build_metric_tables: once per dataset, reduces every GT label row as
 //    utils/text.py::sequence_tokens does (BOS dropped anywhere, stop at the
 //    first EOS, that 0 kept when use_eos) and builds, per video, the sorted
-//    union of the references' packed n-grams with their clip counts (BLEU) and
-//    the ragged reference token rows (ROUGE).
+//    union of the references' packed n-grams with their clip counts (BLEU; and
+//    for leave-one-out scoring the clip count without its only holder) and the
+//    ragged reference token rows (ROUGE).
 //  * bleu4_score_host / rouge_l_score_host: the scorers of eval/metrics.py
 //    (Bleu per-sentence scores, Rouge.calc_score) on those tables, integer
 //    counts and fp64 formulas rounded once to fp32.  They are the
@@ -62,7 +63,11 @@ MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int6
   t.vid_ng_off.resize(Nv + 1);
   t.ref_tok_off.push_back(0);
   std::vector<int> toks;
-  std::map<uint64_t, int> grams, maxc;
+  std::map<uint64_t, int> grams;
+  struct Clip {
+    int m1 = 0, m2 = 0, arg = -1;  // max count, the others' max, its only holder
+  };
+  std::map<uint64_t, Clip> maxc;
   int nref = 0;
   for (int v = 0; v < Nv; ++v) {
     t.vid_ref_off[v] = nref;
@@ -78,9 +83,15 @@ MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int6
                                     std::to_string(toks.size()) + " tokens; at most 64 are "
                                     "supported");
       count_ngrams(toks, grams);
+      const int idx = (int)(r - start[v]);
       for (auto& g : grams) {
-        int& m = maxc[g.first];
-        m = std::max(m, g.second);
+        Clip& c = maxc[g.first];
+        if (g.second > c.m1)
+          c.m2 = c.m1, c.m1 = g.second, c.arg = idx;
+        else if (g.second == c.m1)
+          c.m2 = c.m1, c.arg = -1;
+        else
+          c.m2 = std::max(c.m2, g.second);
       }
       t.ref_len.push_back((int32_t)toks.size());
       t.ref_tok.insert(t.ref_tok.end(), toks.begin(), toks.end());
@@ -98,7 +109,9 @@ MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int6
     }
     for (auto& g : maxc) {  // (std::map: ascending keys)
       t.ng_key.push_back((int64_t)g.first);
-      t.ng_cnt.push_back(g.second);
+      t.ng_cnt.push_back(g.second.m1);
+      t.ng_cnt2.push_back(g.second.m2);
+      t.ng_arg.push_back(g.second.arg);
     }
   }
   t.vid_ref_off[Nv] = nref;
@@ -118,9 +131,11 @@ static void check_hyps(int T, const int64_t* hyp_video, int N, int Nv) {
 
 // correct[4], tlen, rlen of one reduced hypothesis against video v (with
 // references): clipped n-gram matches against the union table, closest
-// reference length with ties to the shorter.
+// reference length with ties to the shorter.  ex: the (absolute) reference left
+// out, -1 for none.
 static void bleu_counts(const std::vector<int>& toks, const MetricTablesView& t, int v,
-                        std::map<uint64_t, int>& grams, int correct[4], int& tlen, int& rlen) {
+                        std::map<uint64_t, int>& grams, int correct[4], int& tlen, int& rlen,
+                        int ex = -1) {
   const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
   count_ngrams(toks, grams);
   const int64_t* k0 = t.ng_key + t.vid_ng_off[v];
@@ -131,22 +146,30 @@ static void bleu_counts(const std::vector<int>& toks, const MetricTablesView& t,
     const int64_t* p = std::lower_bound(
         k0, k1, (int64_t)g.first,
         [](int64_t a, int64_t b) { return (uint64_t)a < (uint64_t)b; });
-    if (p != k1 && *p == (int64_t)g.first)
-      correct[ngram_order(g.first) - 1] += std::min(g.second, t.ng_cnt[p - t.ng_key]);
+    if (p != k1 && *p == (int64_t)g.first) {
+      const int64_t at = p - t.ng_key;
+      const int clip = (ex >= 0 && t.ng_arg[at] == ex - r0) ? t.ng_cnt2[at] : t.ng_cnt[at];
+      correct[ngram_order(g.first) - 1] += std::min(g.second, clip);
+    }
   }
   tlen = (int)toks.size();
   // closest reference length, ties to the shorter: min over (|len_r - tlen|, len_r)
   int best_d = 1 << 30;
   rlen = 0;
   for (int r = r0; r < r1; ++r) {
+    if (r == ex) continue;
     const int d = std::abs(t.ref_len[r] - tlen);
     if (d < best_d || (d == best_d && t.ref_len[r] < rlen)) best_d = d, rlen = t.ref_len[r];
   }
 }
 
 void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
-                      const MetricTablesView& t, int use_eos, float* out) {
+                      const MetricTablesView& t, int use_eos, float* out,
+                      const int64_t* exclude) {
   check_hyps(T, hyp_video, N, t.Nv);
+  // (an empty n-gram table has no rows to hold them)
+  if (exclude && (!t.ng_cnt2 || !t.ng_arg) && t.vid_ng_off[t.Nv] > 0)
+    throw std::invalid_argument("leave-one-out BLEU needs tables with ng_cnt2 / ng_arg");
   const double tiny = 1e-15, small = 1e-9;
   std::vector<int> toks;
   std::map<uint64_t, int> grams;
@@ -158,7 +181,8 @@ void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
       continue;
     }
     int correct[4], tlen, rlen;
-    bleu_counts(toks, t, v, grams, correct, tlen, rlen);
+    bleu_counts(toks, t, v, grams, correct, tlen, rlen,
+                excluded_ref(exclude, i, t.vid_ref_off[v], t.vid_ref_off[v + 1]));
     double b = 1.0;
     for (int k = 0; k < 4; ++k) b *= (correct[k] + tiny) / (std::max(0, tlen - k) + small);
     double s = std::pow(b, 0.25);
@@ -199,7 +223,8 @@ double meteor_score_host(int n_exact, int n_stem, int len_h, int len_r, int chun
 
 void meteor_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                        const MetricTablesView& t, const int32_t* ref_stem,
-                       const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score) {
+                       const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score,
+                       const int64_t* exclude) {
   check_hyps(T, hyp_video, N, t.Nv);
   std::vector<int> toks, hkey, pair_j;
   std::vector<char> used;
@@ -210,7 +235,9 @@ void meteor_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vid
     const int r0 = t.vid_ref_off[v], r1 = t.vid_ref_off[v + 1];
     int best[4] = {0, 0, 0, 0};  // n_exact, n_stem, len_r, chunks
     double best_score = -1.0;
+    const int ex = excluded_ref(exclude, i, r0, r1);
     for (int r = r0; r < r1; ++r) {
+      if (r == ex) continue;
       const int o0 = t.ref_tok_off[r];
       const int n = t.ref_tok_off[r + 1] - o0;
       pair_j.assign(W, -1);
@@ -260,7 +287,8 @@ void meteor_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vid
 }
 
 void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
-                        const MetricTablesView& t, int use_eos, float* out) {
+                        const MetricTablesView& t, int use_eos, float* out,
+                        const int64_t* exclude) {
   check_hyps(T, hyp_video, N, t.Nv);
   const double beta = 1.2, b2 = beta * beta;
   std::vector<int> toks, prev, cur;
@@ -269,7 +297,9 @@ void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vi
     const int v = (int)hyp_video[i];
     const int W = (int)toks.size();
     double p = 0, rc = 0;
+    const int ex = excluded_ref(exclude, i, t.vid_ref_off[v], t.vid_ref_off[v + 1]);
     for (int r = t.vid_ref_off[v]; r < t.vid_ref_off[v + 1]; ++r) {
+      if (r == ex) continue;
       const int32_t* ref = t.ref_tok + t.ref_tok_off[r];
       const int n = t.ref_tok_off[r + 1] - t.ref_tok_off[r];
       prev.assign(W + 1, 0);

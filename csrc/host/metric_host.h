@@ -19,6 +19,11 @@ struct MetricTables {
   std::vector<int32_t> vid_ng_off;   // (Nv + 1)
   std::vector<int64_t> ng_key;
   std::vector<int32_t> ng_cnt;
+  // leave-one-out BLEU: the in-video index of the reference that alone attains
+  // ng_cnt (-1 when several do), and the largest count among the other
+  // references (0 when no other has the n-gram)
+  std::vector<int32_t> ng_cnt2;
+  std::vector<int32_t> ng_arg;
   // ROUGE: the reduced reference token rows, ragged
   std::vector<int32_t> ref_tok_off;  // (nref + 1)
   std::vector<int32_t> ref_tok;
@@ -36,12 +41,16 @@ struct MetricTablesView {
   const int32_t* ng_cnt;
   const int32_t* ref_tok_off;
   const int32_t* ref_tok;
+  // (leave-one-out BLEU only; a view without them scores without exclusion)
+  const int32_t* ng_cnt2 = nullptr;
+  const int32_t* ng_arg = nullptr;
 };
 
 inline MetricTablesView view_of(const MetricTables& t) {
   return {(int)t.vid_ref_off.size() - 1, t.vid_ref_off.data(), t.ref_len.data(),
           t.vid_ng_off.data(),           t.ng_key.data(),      t.ng_cnt.data(),
-          t.ref_tok_off.data(),          t.ref_tok.data()};
+          t.ref_tok_off.data(),          t.ref_tok.data(),     t.ng_cnt2.data(),
+          t.ng_arg.data()};
 }
 
 // Throws std::invalid_argument when a reference is longer than METRIC_MAXT
@@ -55,10 +64,16 @@ MetricTables build_metric_tables(const int64_t* labels, int M, int L, const int6
 // (N, T) hypotheses, T <= METRIC_MAXT (std::invalid_argument otherwise; BLEU
 // also rejects tokens above METRIC_MAX_TOKEN).  A video without references
 // scores 0.
+// exclude (N, optional): leave-one-out scoring, exclude[i] = the in-video index
+// of a reference that hypothesis i does not see (excluded_ref, cider_common.h:
+// ignored when negative, past the video's references, or the only reference).
+// BLEU needs a view with ng_cnt2 / ng_arg for it (std::invalid_argument).
 void bleu4_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
-                      const MetricTablesView& t, int use_eos, float* out);
+                      const MetricTablesView& t, int use_eos, float* out,
+                      const int64_t* exclude = nullptr);
 void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
-                        const MetricTablesView& t, int use_eos, float* out);
+                        const MetricTablesView& t, int use_eos, float* out,
+                        const int64_t* exclude = nullptr);
 
 // Validation scorer (ops/corpus_metrics.py), fp64 host twins of
 // csrc/kernels/corpus_metrics.hip.  Hypotheses are reduced without EOS.
@@ -72,7 +87,8 @@ void bleu_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video
                      const MetricTablesView& t, int32_t* out);
 void meteor_stats_host(const int64_t* hyps, int N, int T, const int64_t* hyp_video,
                        const MetricTablesView& t, const int32_t* ref_stem,
-                       const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score);
+                       const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score,
+                       const int64_t* exclude = nullptr);
 double meteor_score_host(int n_exact, int n_stem, int len_h, int len_r, int chunks);
 
 }  // namespace cst

@@ -19,6 +19,9 @@
 //      (broadcast reads), accumulate min(vh, vr) * vr per order, normalise,
 //      apply exp(-(lh - lr)^2 / (2 * 6^2));
 //   5. score = 10 * sum_refs mean_n(val_n) / n_refs.
+// Leave-one-out (GT consensus scores, ops/consensus.py): exclude[hyp] = e skips
+// reference e of the hypothesis' video (excluded_ref, cider_common.h) and the
+// mean divides by the references used.
 // Deterministic: fixed-order wave/block reductions, no atomics.
 #include "../common.h"
 #include "../cider_common.h"
@@ -39,7 +42,7 @@ __device__ __forceinline__ void cider_body(
     const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_ng_off,
     const float* __restrict__ ref_norm, const int32_t* __restrict__ ref_len,
     const int64_t* __restrict__ ng_key, const float* __restrict__ ng_val, float log_ref_len,
-    int use_eos, float* __restrict__ out) {
+    int use_eos, const int64_t* __restrict__ exclude, float* __restrict__ out) {
   __shared__ int s_tok[CIDER_MAXT];
   __shared__ uint64_t s_key[4][CIDER_MAXT];
   __shared__ float s_val[4][CIDER_MAXT];
@@ -97,8 +100,10 @@ __device__ __forceinline__ void cider_body(
   // -- 4. references, split over the 4 waves --------------------------------------
   const int v = (int)hyp_video[hyp];
   const int r0 = vid_ref_off[v], r1 = vid_ref_off[v + 1];
+  const int ex = excluded_ref(exclude, hyp, r0, r1);  // (leave-one-out: -1 = none)
   float total = 0.f;
   for (int r = r0 + w; r < r1; r += 4) {
+    if (r == ex) continue;  // (wave-uniform)
     float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
     const int g0 = ref_ng_off[r], g1 = ref_ng_off[r + 1];
     for (int g = g0 + lane; g < g1; g += 64) {
@@ -134,7 +139,7 @@ __device__ __forceinline__ void cider_body(
   if (lane == 0) s_part[w] = total;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const int nref = r1 - r0;
+    const int nref = r1 - r0 - (ex >= 0 ? 1 : 0);  // (the references used)
     const float t4 = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
     out[hyp] = nref > 0 ? 10.f * t4 / (4.f * (float)nref) : 0.f;
   }
@@ -146,9 +151,9 @@ __global__ __launch_bounds__(256) void cider_d_kernel(
     const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_ng_off,
     const float* __restrict__ ref_norm, const int32_t* __restrict__ ref_len,
     const int64_t* __restrict__ ng_key, const float* __restrict__ ng_val, float log_ref_len,
-    int use_eos, float* __restrict__ out) {
+    int use_eos, const int64_t* __restrict__ exclude, float* __restrict__ out) {
   cider_body<true>(hyps, T, hyp_video, N, ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off,
-                   ref_norm, ref_len, ng_key, ng_val, log_ref_len, use_eos, out);
+                   ref_norm, ref_len, ng_key, ng_val, log_ref_len, use_eos, exclude, out);
 }
 
 __global__ __launch_bounds__(256) void cider_unclipped_kernel(
@@ -157,22 +162,22 @@ __global__ __launch_bounds__(256) void cider_unclipped_kernel(
     const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_ng_off,
     const float* __restrict__ ref_norm, const int32_t* __restrict__ ref_len,
     const int64_t* __restrict__ ng_key, const float* __restrict__ ng_val, float log_ref_len,
-    int use_eos, float* __restrict__ out) {
+    int use_eos, const int64_t* __restrict__ exclude, float* __restrict__ out) {
   cider_body<false>(hyps, T, hyp_video, N, ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off,
-                    ref_norm, ref_len, ng_key, ng_val, log_ref_len, use_eos, out);
+                    ref_norm, ref_len, ng_key, ng_val, log_ref_len, use_eos, exclude, out);
 }
 
 void launch_cider_d(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
                     const int64_t* ht_keys, const float* ht_vals, uint32_t ht_cap,
                     const int32_t* vid_ref_off, const int32_t* ref_ng_off,
                     const float* ref_norm, const int32_t* ref_len, const int64_t* ng_key,
-                    const float* ng_val, float log_ref_len, int use_eos, float* out,
-                    hipStream_t stream) {
+                    const float* ng_val, float log_ref_len, int use_eos,
+                    const int64_t* exclude, float* out, hipStream_t stream) {
   if (N <= 0) return;
   dim3 grid(N), block(256);
   hipLaunchKernelGGL(cider_d_kernel, grid, block, 0, stream, hyps, T, hyp_video, N, ht_keys,
                      ht_vals, ht_cap, vid_ref_off, ref_ng_off, ref_norm, ref_len, ng_key,
-                     ng_val, log_ref_len, use_eos, out);
+                     ng_val, log_ref_len, use_eos, exclude, out);
   post_launch("cider_d_kernel", stream);
 }
 
@@ -182,12 +187,13 @@ void launch_cider_unclipped(const int64_t* hyps, int T, const int64_t* hyp_video
                             const int32_t* vid_ref_off, const int32_t* ref_ng_off,
                             const float* ref_norm, const int32_t* ref_len,
                             const int64_t* ng_key, const float* ng_val, float log_ref_len,
-                            int use_eos, float* out, hipStream_t stream) {
+                            int use_eos, const int64_t* exclude, float* out,
+                            hipStream_t stream) {
   if (N <= 0) return;
   dim3 grid(N), block(256);
   hipLaunchKernelGGL(cider_unclipped_kernel, grid, block, 0, stream, hyps, T, hyp_video, N,
                      ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off, ref_norm, ref_len, ng_key,
-                     ng_val, log_ref_len, use_eos, out);
+                     ng_val, log_ref_len, use_eos, exclude, out);
   post_launch("cider_unclipped_kernel", stream);
 }
 

@@ -156,14 +156,16 @@ __device__ __forceinline__ double meteor_score(int n_exact, int n_stem, int len_
 //          lower one on equal distance.
 // Chunks: a paired position starts a chunk unless position i - 1 is paired
 // with j - 1.  The reference with the largest score wins, the first on ties.
+// Leave-one-out: exclude[hyp] = e skips reference e of the video (excluded_ref,
+// cider_common.h); best and first-on-ties are over the remaining references.
 // out_stats[hyp] = n_exact, n_stem, len_h, len_r, chunks, n_pairs (6 x int32),
 // out_score[hyp] the segment score (fp64).
 __global__ __launch_bounds__(64 * CM_WAVES) void meteor_stats_kernel(
     const int64_t* __restrict__ hyps, int T, const int64_t* __restrict__ hyp_video, int N,
     int Nv, const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_tok_off,
     const int32_t* __restrict__ ref_tok, const int32_t* __restrict__ ref_stem,
-    const int32_t* __restrict__ stem_ids, int V, int32_t* __restrict__ out_stats,
-    double* __restrict__ out_score) {
+    const int32_t* __restrict__ stem_ids, int V, const int64_t* __restrict__ exclude,
+    int32_t* __restrict__ out_stats, double* __restrict__ out_score) {
   __shared__ int s_tok[CM_WAVES][CM_MAXT];
 
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -185,7 +187,9 @@ __global__ __launch_bounds__(64 * CM_WAVES) void meteor_stats_kernel(
 
   int b_exact = 0, b_stem = 0, b_lr = 0, b_chunks = 0;
   double b_score = -1.0;
+  const int ex = excluded_ref(exclude, hyp, r0, r1);  // (leave-one-out: -1 = none)
   for (int r = r0; r < r1; ++r) {
+    if (r == ex) continue;  // (wave-uniform)
     const int o0 = ref_tok_off[r];
     const int n = min(ref_tok_off[r + 1] - o0, 64);
     const int rtok = lane < n ? ref_tok[o0 + lane] : -2;
@@ -256,12 +260,12 @@ void launch_bleu_stats(const int64_t* hyps, int T, const int64_t* hyp_video, int
 void launch_meteor_stats(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
                          const int32_t* vid_ref_off, const int32_t* ref_tok_off,
                          const int32_t* ref_tok, const int32_t* ref_stem,
-                         const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score,
-                         hipStream_t stream) {
+                         const int32_t* stem_ids, int V, const int64_t* exclude,
+                         int32_t* out_stats, double* out_score, hipStream_t stream) {
   if (N <= 0) return;
   dim3 grid((N + CM_WAVES - 1) / CM_WAVES), block(64 * CM_WAVES);
   hipLaunchKernelGGL(meteor_stats_kernel, grid, block, 0, stream, hyps, T, hyp_video, N, Nv,
-                     vid_ref_off, ref_tok_off, ref_tok, ref_stem, stem_ids, V, out_stats,
+                     vid_ref_off, ref_tok_off, ref_tok, ref_stem, stem_ids, V, exclude, out_stats,
                      out_score);
   post_launch("meteor_stats_kernel", stream);
 }

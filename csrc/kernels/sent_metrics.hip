@@ -48,11 +48,18 @@ __device__ __forceinline__ int wave_min_i(int v) {
 //      into one int (both fields <= 64);
 //   5. lane 0: prod_k (correct_k + 1e-15) / (guess_k + 1e-9), ^(1/4), brevity
 //      penalty exp(1 - 1/ratio) when ratio < 1; a video without references: 0.
+// Leave-one-out (exclude[hyp] = e, excluded_ref in cider_common.h): the clip
+// count is a maximum over the references, so the table keeps per union n-gram
+// the reference that alone attains it (ng_arg, -1 when several do) and the
+// largest count among the others (ng_cnt2): clip = ng_arg == e ? ng_cnt2 :
+// ng_cnt; the closest-length reduction skips reference e.
 __global__ __launch_bounds__(64 * SM_WAVES) void bleu4_kernel(
     const int64_t* __restrict__ hyps, int T, const int64_t* __restrict__ hyp_video, int N,
     int Nv, const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_len,
     const int32_t* __restrict__ vid_ng_off, const int64_t* __restrict__ ng_key,
-    const int32_t* __restrict__ ng_cnt, int use_eos, float* __restrict__ out) {
+    const int32_t* __restrict__ ng_cnt, const int32_t* __restrict__ ng_cnt2,
+    const int32_t* __restrict__ ng_arg, int use_eos, const int64_t* __restrict__ exclude,
+    float* __restrict__ out) {
   __shared__ int s_tok[SM_WAVES][SM_MAXT];
   __shared__ uint64_t s_key[SM_WAVES][4][SM_MAXT];
   __shared__ int s_tf[SM_WAVES][4][SM_MAXT];
@@ -107,11 +114,16 @@ __global__ __launch_bounds__(64 * SM_WAVES) void bleu4_kernel(
   const bool vok = v64 >= 0 && v64 < Nv;  // (a video outside the tables scores 0)
   const int v = vok ? (int)v64 : 0;
   const int r0 = vid_ref_off[v], r1 = vok ? vid_ref_off[v + 1] : r0;
+  // leave-one-out: the in-video index of the reference left out, -1 for none
+  // (wave-uniform; only then are ng_cnt2 / ng_arg read)
+  const int ex = excluded_ref(exclude, hyp, r0, r1);
+  const int e = ex >= 0 ? ex - r0 : -1;
   int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
   const int g0 = vid_ng_off[v], g1 = vok ? vid_ng_off[v + 1] : g0;
   for (int g = g0 + lane; g < g1; g += 64) {
     const uint64_t key = (uint64_t)ng_key[g];
-    const int clip = ng_cnt[g];
+    int clip = ng_cnt[g];
+    if (e >= 0 && ng_arg[g] == e) clip = ng_cnt2[g];  // (0: adds nothing)
     const int n = ngram_order(key) - 1;
     const int cnt = W - n;
     int c = 0;
@@ -127,7 +139,7 @@ __global__ __launch_bounds__(64 * SM_WAVES) void bleu4_kernel(
   int best = 0x7fffffff;
   for (int r = r0 + lane; r < r1; r += 64) {
     const int lr = ref_len[r];
-    best = min(best, (abs(lr - W) << 8) | lr);
+    if (r != ex) best = min(best, (abs(lr - W) << 8) | lr);
   }
   best = wave_min_i(best);
   if (lane == 0) {
@@ -160,10 +172,12 @@ __global__ __launch_bounds__(64 * SM_WAVES) void bleu4_kernel(
 // tracked separately as exact integer fractions (cross-multiplied compares;
 // the correctly rounded quotient of the largest fraction is the largest of the
 // rounded quotients) and divided once in double at the end.
+// Leave-one-out: exclude[hyp] = e skips reference e of the video (excluded_ref).
 __global__ __launch_bounds__(64 * SM_WAVES) void rouge_l_kernel(
     const int64_t* __restrict__ hyps, int T, const int64_t* __restrict__ hyp_video, int N,
     int Nv, const int32_t* __restrict__ vid_ref_off, const int32_t* __restrict__ ref_tok_off,
-    const int32_t* __restrict__ ref_tok, int use_eos, float* __restrict__ out) {
+    const int32_t* __restrict__ ref_tok, int use_eos, const int64_t* __restrict__ exclude,
+    float* __restrict__ out) {
   __shared__ int s_tok[SM_WAVES][SM_MAXT];
 
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -182,20 +196,27 @@ __global__ __launch_bounds__(64 * SM_WAVES) void rouge_l_kernel(
   const int r0 = vid_ref_off[v], r1 = vok ? vid_ref_off[v + 1] : r0;
   int best_l = 0;             // max lcs (precision: the denominator len_h is shared)
   int rec_l = 0, rec_n = 1;   // max lcs / len_r as a fraction
+  // leave-one-out: the loop walks the references other than `ex` (-1: all of
+  // them); `r` is the reference being processed, `rn` the one after it, both
+  // stepped over `ex`, so the prefetch never loads the excluded row
+  const int ex = excluded_ref(exclude, hyp, r0, r1);
   int o0 = 0, o1 = 0, nxt = -2;
-  if (r0 < r1) {
-    o0 = ref_tok_off[r0];
-    o1 = ref_tok_off[r0 + 1];
+  int r = r0 == ex ? r0 + 1 : r0;
+  if (r < r1) {
+    o0 = ref_tok_off[r];
+    o1 = ref_tok_off[r + 1];
     nxt = lane < min(o1 - o0, 64) ? ref_tok[o0 + lane] : -2;
   }
-  for (int r = r0; r < r1; ++r) {
+  while (r < r1) {
     const int n = min(o1 - o0, 64);
     const int rtok = nxt;
-    if (r + 1 < r1) {  // prefetch the next reference
-      o0 = o1;
-      o1 = ref_tok_off[r + 2];
+    const int rn = r + 1 == ex ? r + 2 : r + 1;
+    if (rn < r1) {  // prefetch the next reference
+      o0 = ref_tok_off[rn];
+      o1 = ref_tok_off[rn + 1];
       nxt = lane < min(o1 - o0, 64) ? ref_tok[o0 + lane] : -2;
     }
+    r = rn;
     uint64_t V = ~0ull;
     for (int a = 0; a < n; ++a) {
       const int c = __builtin_amdgcn_readlane(rtok, a);
@@ -221,22 +242,25 @@ __global__ __launch_bounds__(64 * SM_WAVES) void rouge_l_kernel(
 
 void launch_bleu4(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
                   const int32_t* vid_ref_off, const int32_t* ref_len, const int32_t* vid_ng_off,
-                  const int64_t* ng_key, const int32_t* ng_cnt, int use_eos, float* out,
+                  const int64_t* ng_key, const int32_t* ng_cnt, const int32_t* ng_cnt2,
+                  const int32_t* ng_arg, int use_eos, const int64_t* exclude, float* out,
                   hipStream_t stream) {
+  if (!ng_cnt2 || !ng_arg) exclude = nullptr;  // (callers check: no tables, no exclusion)
   if (N <= 0) return;
   dim3 grid((N + SM_WAVES - 1) / SM_WAVES), block(64 * SM_WAVES);
   hipLaunchKernelGGL(bleu4_kernel, grid, block, 0, stream, hyps, T, hyp_video, N, Nv, vid_ref_off,
-                     ref_len, vid_ng_off, ng_key, ng_cnt, use_eos, out);
+                     ref_len, vid_ng_off, ng_key, ng_cnt, ng_cnt2, ng_arg, use_eos, exclude, out);
   post_launch("bleu4_kernel", stream);
 }
 
 void launch_rouge_l(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
                     const int32_t* vid_ref_off, const int32_t* ref_tok_off,
-                    const int32_t* ref_tok, int use_eos, float* out, hipStream_t stream) {
+                    const int32_t* ref_tok, int use_eos, const int64_t* exclude, float* out,
+                    hipStream_t stream) {
   if (N <= 0) return;
   dim3 grid((N + SM_WAVES - 1) / SM_WAVES), block(64 * SM_WAVES);
   hipLaunchKernelGGL(rouge_l_kernel, grid, block, 0, stream, hyps, T, hyp_video, N, Nv, vid_ref_off,
-                     ref_tok_off, ref_tok, use_eos, out);
+                     ref_tok_off, ref_tok, use_eos, exclude, out);
   post_launch("rouge_l_kernel", stream);
 }
 

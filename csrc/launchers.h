@@ -55,12 +55,14 @@ struct BeamFusedArgs {
 void launch_beam_fused_step(const BeamFusedArgs& a, int t, hipStream_t stream);
 
 // cider_d.hip
+// (exclude, here and in the metric launchers below: nullable (N) int64, the
+// in-video index of a reference each hypothesis leaves out; cider_common.h)
 void launch_cider_d(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
                     const int64_t* ht_keys, const float* ht_vals, uint32_t ht_cap,
                     const int32_t* vid_ref_off, const int32_t* ref_ng_off,
                     const float* ref_norm, const int32_t* ref_len, const int64_t* ng_key,
-                    const float* ng_val, float log_ref_len, int use_eos, float* out,
-                    hipStream_t stream);
+                    const float* ng_val, float log_ref_len, int use_eos,
+                    const int64_t* exclude, float* out, hipStream_t stream);
 
 // (coco CIDEr: no clipping, no length penalty; same tables, T <= 64)
 void launch_cider_unclipped(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
@@ -68,17 +70,20 @@ void launch_cider_unclipped(const int64_t* hyps, int T, const int64_t* hyp_video
                             const int32_t* vid_ref_off, const int32_t* ref_ng_off,
                             const float* ref_norm, const int32_t* ref_len,
                             const int64_t* ng_key, const float* ng_val, float log_ref_len,
-                            int use_eos, float* out, hipStream_t stream);
+                            int use_eos, const int64_t* exclude, float* out,
+                            hipStream_t stream);
 
 // sent_metrics.hip: sentence BLEU-4 / ROUGE-L of N hypotheses (T <= 64), one
 // wavefront each, against the tables of host/metric_host.h (Nv videos)
 void launch_bleu4(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
                   const int32_t* vid_ref_off, const int32_t* ref_len, const int32_t* vid_ng_off,
-                  const int64_t* ng_key, const int32_t* ng_cnt, int use_eos, float* out,
+                  const int64_t* ng_key, const int32_t* ng_cnt, const int32_t* ng_cnt2,
+                  const int32_t* ng_arg, int use_eos, const int64_t* exclude, float* out,
                   hipStream_t stream);
 void launch_rouge_l(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
                     const int32_t* vid_ref_off, const int32_t* ref_tok_off,
-                    const int32_t* ref_tok, int use_eos, float* out, hipStream_t stream);
+                    const int32_t* ref_tok, int use_eos, const int64_t* exclude, float* out,
+                    hipStream_t stream);
 
 // corpus_metrics.hip: per-hypothesis statistics of corpus BLEU (10 x int32) and
 // METEOR (6 x int32 + the fp64 segment score), one wavefront each (T <= 64)
@@ -89,8 +94,8 @@ void launch_bleu_stats(const int64_t* hyps, int T, const int64_t* hyp_video, int
 void launch_meteor_stats(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,
                          const int32_t* vid_ref_off, const int32_t* ref_tok_off,
                          const int32_t* ref_tok, const int32_t* ref_stem,
-                         const int32_t* stem_ids, int V, int32_t* out_stats, double* out_score,
-                         hipStream_t stream);
+                         const int32_t* stem_ids, int V, const int64_t* exclude,
+                         int32_t* out_stats, double* out_score, hipStream_t stream);
 
 // adam.hip
 // bf16 shadow copies of decoder weights written by the optimizer pass

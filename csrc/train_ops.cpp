@@ -228,9 +228,22 @@ at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, in
   return dlp;
 }
 
+// Leave-one-out scoring: the optional (N) int64 device array of the metric
+// scorers, exclude[h] = the in-video index of a reference hypothesis h does not
+// see (cider_common.h excluded_ref).  Null when not given.
+static const int64_t* exclude_ptr(const c10::optional<at::Tensor>& exclude, int64_t N) {
+  if (!exclude.has_value() || !exclude->defined()) return nullptr;
+  check_cuda(*exclude, "exclude");
+  TORCH_CHECK(exclude->scalar_type() == at::kLong && exclude->dim() == 1 &&
+                  exclude->size(0) == N && exclude->is_contiguous(),
+              "exclude: contiguous int64 (N)");
+  return exclude->data_ptr<int64_t>();
+}
+
 // On-GPU CIDEr-D scores of N hypotheses.
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
-                       double log_ref_len, int64_t use_eos, bool clipped) {
+                       double log_ref_len, int64_t use_eos, bool clipped,
+                       c10::optional<at::Tensor> exclude) {
   check_cuda(hyps, "hyps");
   check_cuda(hyp_video, "hyp_video");
   TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
@@ -246,15 +259,16 @@ at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::stri
                  (uint32_t)t["ht_keys"].numel(), t["vid_ref_off"].data_ptr<int32_t>(),
                  t["ref_ng_off"].data_ptr<int32_t>(), t["ref_norm"].data_ptr<float>(),
                  t["ref_len"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
-                 t["ng_val"].data_ptr<float>(), (float)log_ref_len, (int)use_eos, out.data_ptr<float>(),
-                 cur_stream());
+                 t["ng_val"].data_ptr<float>(), (float)log_ref_len, (int)use_eos,
+                 exclude_ptr(exclude, N), out.data_ptr<float>(), cur_stream());
   return out;
 }
 
 // On-GPU sentence BLEU-4 / ROUGE-L scores of N hypotheses (kernels/sent_metrics.hip).
 // No allocation besides the result and no synchronisation: capturable.
 at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
-                        std::map<std::string, at::Tensor> t, int64_t use_eos) {
+                        std::map<std::string, at::Tensor> t, int64_t use_eos,
+                        c10::optional<at::Tensor> exclude) {
   check_cuda(hyps, "hyps");
   check_cuda(hyp_video, "hyp_video");
   TORCH_CHECK(hyps.dim() == 2 && hyp_video.dim() == 1 && hyp_video.size(0) == hyps.size(0),
@@ -277,17 +291,29 @@ at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor h
   TORCH_CHECK(Nv >= 0 && t["vid_ng_off"].numel() == Nv + 1 &&
                   t["ref_tok_off"].numel() == t["ref_len"].numel() + 1,
               "metric tables are inconsistent");
+  const int64_t* ex = exclude_ptr(exclude, N);
+  const int32_t *cnt2 = nullptr, *arg = nullptr;
+  if (bleu && ex) {  // (leave-one-out BLEU: the clip counts without their only holder)
+    for (const char* k : {"ng_cnt2", "ng_arg"}) {
+      TORCH_CHECK(t.count(k), "metric tables lack ", k, " (leave-one-out BLEU)");
+      check_cuda(t[k], k);
+      TORCH_CHECK(t[k].scalar_type() == at::kInt && t[k].is_contiguous() &&
+                      t[k].numel() == t["ng_key"].numel(),
+                  "metric table ", k, " has the wrong dtype or size");
+    }
+    cnt2 = t["ng_cnt2"].data_ptr<int32_t>(), arg = t["ng_arg"].data_ptr<int32_t>();
+  }
   at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
   if (bleu)
     launch_bleu4(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
                  t["vid_ref_off"].data_ptr<int32_t>(), t["ref_len"].data_ptr<int32_t>(),
                  t["vid_ng_off"].data_ptr<int32_t>(), t["ng_key"].data_ptr<int64_t>(),
-                 t["ng_cnt"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
-                 cur_stream());
+                 t["ng_cnt"].data_ptr<int32_t>(), cnt2, arg, (int)use_eos, ex,
+                 out.data_ptr<float>(), cur_stream());
   else
     launch_rouge_l(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
                    t["vid_ref_off"].data_ptr<int32_t>(), t["ref_tok_off"].data_ptr<int32_t>(),
-                   t["ref_tok"].data_ptr<int32_t>(), (int)use_eos, out.data_ptr<float>(),
+                   t["ref_tok"].data_ptr<int32_t>(), (int)use_eos, ex, out.data_ptr<float>(),
                    cur_stream());
   return out;
 }
@@ -335,7 +361,8 @@ at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::strin
 }
 
 std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
-                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids) {
+                                     std::map<std::string, at::Tensor> t, at::Tensor stem_ids,
+                                     c10::optional<at::Tensor> exclude) {
   const int Nv = check_corpus_inputs(hyps, hyp_video, t,
                                      {"vid_ref_off", "ref_len", "ref_tok_off", "ref_tok",
                                       "ref_stem"});
@@ -352,7 +379,7 @@ std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
   launch_meteor_stats(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, Nv,
                       t["vid_ref_off"].data_ptr<int32_t>(), t["ref_tok_off"].data_ptr<int32_t>(),
                       t["ref_tok"].data_ptr<int32_t>(), t["ref_stem"].data_ptr<int32_t>(),
-                      stem_ids.data_ptr<int32_t>(), (int)stem_ids.numel(),
+                      stem_ids.data_ptr<int32_t>(), (int)stem_ids.numel(), exclude_ptr(exclude, N),
                       stats.data_ptr<int32_t>(), score.data_ptr<double>(), cur_stream());
   return {stats, score};
 }

@@ -34,13 +34,19 @@ def seed_everything(seed, rank=0):
 
 
 def load_splits(opt):
+    tokens = getattr(opt, 'consensus_scorer', 'file') == 'tokens'
+    if tokens and opt.train_bcmrscores_pkl:
+        raise ValueError('--consensus_scorer tokens computes the consensus scores itself; '
+                         '--train_bcmrscores_pkl must not be given with it')
     if opt.synthetic:
         n = opt.synthetic_videos or None
         return make_splits(opt.synthetic, vocab_size=opt.synthetic_vocab,
                            seq_length=opt.seq_length, feat_dims=opt.feat_dims,
                            num_chunks=opt.num_chunks, train_videos=n, seed=opt.seed,
-                           with_consensus=bool(opt.use_cst and opt.scb_baseline == 1) or
-                           bool(opt.use_cst and not opt.use_mixer),
+                           # (--consensus_scorer tokens: the trainer computes them)
+                           with_consensus=not tokens and (
+                               bool(opt.use_cst and opt.scb_baseline == 1) or
+                               bool(opt.use_cst and not opt.use_mixer)),
                            seq_per_img=opt.train_seq_per_img)
     df = opt.train_cached_tokens if isinstance(opt.train_cached_tokens, str) else None
     tr = VideoCaptionDataset.from_files(opt.train_label_h5, opt.train_feat_h5, opt.num_chunks,

@@ -106,6 +106,11 @@ def build_parser():
         help='validation / test metrics: strings = decoded sentences through the Python '
              'scorers (reference route); tokens = token ids against the split\'s label table, '
              'on the GPU when the model runs there (ops/corpus_metrics.py)')
+    add('--consensus_scorer', type=str, default='file', choices=['file', 'tokens'],
+        help='GT consensus scores of CST / WXE training: file = read --train_bcmrscores_pkl '
+             '(prepro/evalscores.py); tokens = computed at start-up (when --use_cst 1) from the training label '
+             'table in the metric of --eval_metric, leave-one-out, on the GPU when the model '
+             'runs there (ops/consensus.py); --train_bcmrscores_pkl must then not be given')
     add('--mask_after_eos', type=int, default=0,
         help='fix for SURVEY §2.8.1: mask MIXER tokens sampled after EOS (0 = reference parity)')
     add('--dedupe_greedy', type=int, default=1,

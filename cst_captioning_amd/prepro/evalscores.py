@@ -10,6 +10,11 @@ with fewer than ``seq_per_img`` captions are supported by cycling their
 captions (slot ``i`` uses caption ``i % ncap``), so MSVD-style data works.
 Results are saved as ``.npz`` (no pickle needed to read them back); a
 ``.pkl`` path also gets the reference-format pickle.
+
+``--scorer tokens`` scores the label rows of ``--label_file`` in token space
+instead (:mod:`..ops.consensus`: the native scorers, on the GPU when there is
+one; CIDEr is then the reward's CIDEr-D with the ``--cached_tokens`` document
+frequencies) and writes the same layout, rows in the label file's video order.
 """
 import argparse
 import os
@@ -75,15 +80,49 @@ def load_scores(path, metric='CIDEr'):
     return np.asarray(z[metric], dtype=np.float64)
 
 
+def compute_token_consensus_scores(label_file, cached_tokens=None, seq_per_img=20,
+                                   remove_in_ref=True, use_eos=0, device=None):
+    """The four metrics of :class:`..ops.consensus.ConsensusScorer` for the
+    label file's captions (CIDEr only with a ``cached_tokens`` df file)."""
+    import torch
+    from ..data import formats
+    from ..data.dataset import VideoCaptionDataset
+    from ..ops.consensus import ConsensusScorer
+    store = formats.load_label_file(label_file)
+    df = None
+    if cached_tokens:
+        from .ciderdf import load_packed_df
+        df = load_packed_df(cached_tokens)
+    ds = VideoCaptionDataset(store['vocab'], store['videos'], [], store.get('labels'),
+                             store.get('label_start_ix'), store.get('label_end_ix'), df=df)
+    if device is None:
+        device = 'cuda' if torch.cuda.is_available() else 'cpu'
+    metrics = tuple(m for m in METRICS if m != 'CIDEr' or df is not None)
+    return ConsensusScorer(ds, use_eos=use_eos, device=device).scores(seq_per_img, metrics,
+                                                                      remove_in_ref)
+
+
 def main(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('cocofmt_file')
+    p.add_argument('cocofmt_file', help='gold captions (--scorer strings; unused with tokens)')
     p.add_argument('output_pkl')
     p.add_argument('--seq_per_img', type=int, default=20)
     p.add_argument('--remove_in_ref', action='store_true')
+    p.add_argument('--scorer', default='strings', choices=['strings', 'tokens'],
+                   help='strings: the Python scorers on the coco-format captions; tokens: the '
+                        'native token-space scorers on the label rows (ops/consensus.py)')
+    p.add_argument('--label_file', help='--scorer tokens: the split\'s label file')
+    p.add_argument('--cached_tokens', help='--scorer tokens: CIDEr-D document-frequency file')
+    p.add_argument('--use_eos', type=int, default=0, help='--scorer tokens: as in training')
     a = p.parse_args(argv)
-    scores = compute_consensus_scores(load_gt_refs(a.cocofmt_file), a.seq_per_img,
-                                      a.remove_in_ref)
+    if a.scorer == 'tokens':
+        if not a.label_file or not a.cached_tokens:
+            p.error('--scorer tokens needs --label_file and --cached_tokens')
+        scores = compute_token_consensus_scores(a.label_file, a.cached_tokens, a.seq_per_img,
+                                                a.remove_in_ref, a.use_eos)
+    else:
+        scores = compute_consensus_scores(load_gt_refs(a.cocofmt_file), a.seq_per_img,
+                                          a.remove_in_ref)
     save_scores(a.output_pkl, scores)
     return scores
 

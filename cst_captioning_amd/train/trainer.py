@@ -167,6 +167,14 @@ class Trainer:
         if engine is not None:
             engine.attach_optimizer(self)
         self.scorer = None
+        # --consensus_scorer tokens: the training split's GT consensus scores
+        # from its label table, before the first batch caches the dataset's
+        # device tensors (ops/consensus.py; every rank computes the same table)
+        if (getattr(opt, 'consensus_scorer', 'file') == 'tokens' and opt.use_cst == 1
+                and train_loader is not None and train_loader.mode == 'train'
+                and train_loader.has_label):
+            from ..ops.consensus import set_token_consensus
+            set_token_consensus(opt, train_loader.ds, self.device)
         # SCST with the fused engine: X = E W launched right after the rollout
         # (engine.launch_x); False keeps the backward's own E' W GEMM (tests)
         self.use_x_after_rollout = True
