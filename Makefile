@@ -73,6 +73,11 @@ USE_EOS?=0
 # table (compute_evalscores writes the same file layout; train computes them at
 # start-up and reads no file)
 CONSENSUS_SCORER?=file
+# validation / test decoding: standard (greedy or beam), or mbr = consensus
+# decoding over the standard caption + MBR_SAMPLES samples at MBR_TEMPERATURE
+DECODE?=standard
+MBR_SAMPLES?=20
+MBR_TEMPERATURE?=1.0
 USE_MIXER?=0
 MIXER_FROM?=-1
 SS_K?=100
@@ -170,11 +175,20 @@ TRAIN_OPT=--beam_size $(BEAM_SIZE) --max_patience $(MAX_PATIENCE) --eval_metric 
 	--use_rl $(USE_RL) --use_mixer $(USE_MIXER) --mixer_from $(MIXER_FROM) \
 	--use_cst $(USE_CST) --scb_captions $(SCB_CAPTIONS) --scb_baseline $(SCB_BASELINE) \
 	--loglevel $(LOGLEVEL) --model_type $(MODEL_TYPE) --use_eos $(USE_EOS) \
+	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
 	--model_file $@ --start_from $(START_FROM) --result_file $(basename $@)_test.json \
 	2>&1 | tee $(basename $@).log
 
+# consensus decoding at test time scores under the training set's df table
+ifeq ($(DECODE),mbr)
+MBR_TEST_OPT=--use_eos $(USE_EOS) --train_cached_tokens $(META_DIR)/$(TRAIN_DATASET)_train_ciderdf.pkl
+else
+MBR_TEST_OPT=
+endif
 TEST_OPT=--beam_size $(BEAM_SIZE) --language_eval $(VAL_LANG_EVAL) --test_seq_per_img $(TEST_SEQ_PER_IMG) \
-	--test_batch_size $(BATCH_SIZE) --loglevel $(LOGLEVEL) --result_file $@
+	--test_batch_size $(BATCH_SIZE) --loglevel $(LOGLEVEL) --result_file $@ \
+	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
+	$(MBR_TEST_OPT)
 
 train: $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth
 $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth: \

@@ -63,7 +63,29 @@ static const int64_t* cpu_exclude(const c10::optional<at::Tensor>& exclude, int6
 static at::Tensor cider_score_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                   std::map<std::string, at::Tensor> t, double log_ref_len,
                                   int64_t use_eos, bool clipped,
-                                  c10::optional<at::Tensor> exclude) {
+                                  c10::optional<at::Tensor> exclude, int64_t group) {
+  if (group != 0) {  // peer mode: every row against the others of its pool of `group`
+    TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2, "CPU hyps (N, T)");
+    TORCH_CHECK(group >= 2, "cider_score_cpu: group = ", group,
+                "; a peer pool has at least 2 rows (group = 0: reference tables)");
+    TORCH_CHECK(clipped && !(exclude.has_value() && exclude->defined()),
+                "cider_score_cpu: peer mode (group > 0) is CIDEr-D without exclude: clipped must "
+                "be True and exclude None");
+    TORCH_CHECK(hyps.size(0) % group == 0, "cider_score_cpu: ", hyps.size(0),
+                " rows are not whole pools of ", group);
+    TORCH_CHECK(t.count("ht_keys") && t.count("ht_vals"), "tables: ht_keys and ht_vals");
+    hyps = hyps.contiguous().to(at::kLong);
+    at::Tensor hk = t["ht_keys"].contiguous().to(at::kLong);
+    at::Tensor hv = t["ht_vals"].contiguous().to(at::kFloat);
+    TORCH_CHECK(!hk.is_cuda() && !hv.is_cuda() && hk.numel() == hv.numel() && hk.numel() > 0 &&
+                    (hk.numel() & (hk.numel() - 1)) == 0,
+                "df hash table: CPU keys and values of one power-of-two size");
+    at::Tensor out = at::empty({hyps.size(0)}, at::TensorOptions().dtype(at::kFloat));
+    cider_peers_host(hyps.data_ptr<int64_t>(), (int)hyps.size(0), (int)hyps.size(1), (int)group,
+                     hk.data_ptr<int64_t>(), hv.data_ptr<float>(), (uint32_t)hk.numel(),
+                     log_ref_len, (int)use_eos, out.data_ptr<float>());
+    return out;
+  }
   hyps = hyps.contiguous().to(at::kLong);
   hyp_video = hyp_video.contiguous().to(at::kLong);
   at::Tensor ex_keep;
@@ -196,12 +218,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // exclude (here and in the metric scorers below): optional (N) int64, the
   // in-video index of a reference each hypothesis leaves out (leave-one-out
   // scoring of GT captions, ops/consensus.py); negative entries leave none out
+  // group = G >= 2: peer mode (consensus / MBR decoding, ops/mbr.py): hyps is B
+  // pools of G rows, every row scored against the others of its pool; only
+  // ht_keys / ht_vals of tables are read, hyp_video is ignored (0: as before)
   m.def("cider_score", &cst::cider_score, py::arg("hyps"), py::arg("hyp_video"),
         py::arg("tables"), py::arg("log_ref_len"), py::arg("use_eos"),
-        py::arg("clipped") = true, py::arg("exclude") = py::none());
+        py::arg("clipped") = true, py::arg("exclude") = py::none(), py::arg("group") = 0);
   m.def("cider_score_cpu", &cst::cider_score_cpu, py::arg("hyps"), py::arg("hyp_video"),
         py::arg("tables"), py::arg("log_ref_len"), py::arg("use_eos"),
-        py::arg("clipped") = true, py::arg("exclude") = py::none());
+        py::arg("clipped") = true, py::arg("exclude") = py::none(), py::arg("group") = 0);
   m.def("metric_build_tables", &cst::metric_build_tables, py::arg("labels"), py::arg("start"),
         py::arg("end"), py::arg("use_eos"), py::arg("stem_ids") = py::none(),
         "sentence BLEU-4 / ROUGE-L reference tables of a dataset (dict of CPU tensors); with "

@@ -91,7 +91,7 @@ at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
                               at::Tensor dloss);
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
                        double log_ref_len, int64_t use_eos, bool clipped,
-                       c10::optional<at::Tensor> exclude);
+                       c10::optional<at::Tensor> exclude, int64_t group);
 at::Tensor bleu_stats(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t);
 std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
                                      std::map<std::string, at::Tensor> t, at::Tensor stem_ids,

@@ -7,10 +7,13 @@
 //    and builds the open-addressing df hash table the GPU kernel probes.
 //  * cider_score_host: the same scorer in double precision on the CPU (used
 //    when no GPU is present and as a fast oracle in tests).
+//  * cider_peers_host: peer scoring (consensus / MBR decoding) in double
+//    precision, the twin of kernels/cider_pairwise.hip.
 #include "cider_host.h"
 
 #include <algorithm>
 #include <cmath>
+#include <stdexcept>
 #include <unordered_map>
 
 #include "../cider_common.h"
@@ -137,6 +140,68 @@ void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
     }
     const int nref = r1 - r0 - (ex >= 0 ? 1 : 0);
     out[i] = (nref > 0) ? (float)(10.0 * total / (4.0 * nref)) : 0.f;
+  }
+}
+
+// One pool row's CIDEr-D vector in fp64: sorted unique n-grams with tf-idf
+// values, per-order norms, length.
+struct PeerVec {
+  std::vector<std::pair<uint64_t, double>> g;
+  double norm[4];
+  double len;
+};
+
+void cider_peers_host(const int64_t* hyps, int N, int T, int G, const int64_t* ht_keys,
+                      const float* ht_vals, uint32_t ht_cap, double log_ref_len, int use_eos,
+                      float* out) {
+  if (G < 2 || N % G != 0) throw std::invalid_argument("cider_peers_host: N rows in pools of G >= 2");
+  std::vector<int> toks;
+  std::vector<std::pair<uint64_t, int>> grams;
+  std::vector<PeerVec> pool((size_t)G);
+  for (int p0 = 0; p0 < N; p0 += G) {
+    for (int r = 0; r < G; ++r) {
+      compact_tokens(hyps + (int64_t)(p0 + r) * T, T, use_eos, toks);
+      count_ngrams(toks, grams);
+      PeerVec& v = pool[r];
+      v.g.clear();
+      for (int n = 0; n < 4; ++n) v.norm[n] = 0;
+      for (auto& g : grams) {
+        const float df = df_lookup(ht_keys, ht_vals, ht_cap, g.first);
+        const double val = (double)g.second * (log_ref_len - std::log(std::max(1.0, (double)df)));
+        v.g.emplace_back(g.first, val);
+        v.norm[ngram_order(g.first) - 1] += val * val;
+      }
+      for (int n = 0; n < 4; ++n) v.norm[n] = std::sqrt(v.norm[n]);
+      v.len = std::max((int)toks.size() - 1, 0);
+    }
+    for (int i = 0; i < G; ++i) {
+      const PeerVec& h = pool[i];
+      double total = 0;
+      for (int j = 0; j < G; ++j) {
+        if (j == i) continue;
+        const PeerVec& r = pool[j];
+        double acc[4] = {0, 0, 0, 0};
+        size_t a = 0, b = 0;  // (both sorted by key)
+        while (a < h.g.size() && b < r.g.size()) {
+          if (h.g[a].first < r.g[b].first) {
+            ++a;
+          } else if (r.g[b].first < h.g[a].first) {
+            ++b;
+          } else {
+            acc[ngram_order(r.g[b].first) - 1] += std::min(h.g[a].second, r.g[b].second) * r.g[b].second;
+            ++a, ++b;
+          }
+        }
+        const double delta = h.len - r.len;
+        const double pen = std::exp(-(delta * delta) / 72.0);
+        for (int n = 0; n < 4; ++n) {
+          double val = acc[n];
+          if (h.norm[n] != 0 && r.norm[n] != 0) val /= (h.norm[n] * r.norm[n]);
+          total += val * pen;
+        }
+      }
+      out[p0 + i] = (float)(10.0 * total / (4.0 * (G - 1)));
+    }
   }
 }
 

@@ -40,4 +40,14 @@ void cider_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vide
                       const CiderTablesView& t, double log_ref_len, int use_eos, float* out,
                       bool clipped = true, const int64_t* exclude = nullptr);
 
+// Peer scoring (consensus / MBR decoding): hyps (N, T) in pools of G consecutive
+// rows; out[i] = 10 x the mean over the G - 1 other rows j of i's pool of the
+// CIDEr-D similarity with i as the hypothesis and j as the reference -- i.e.
+// build_cider_tables on the pool rows + cider_score_host with exclude[i] = i mod G.
+// Only the df hash table is read.  Any G >= 2 with N % G == 0 (else
+// std::invalid_argument); identical rows of a pool are ordinary peers.
+void cider_peers_host(const int64_t* hyps, int N, int T, int G, const int64_t* ht_keys,
+                      const float* ht_vals, uint32_t ht_cap, double log_ref_len, int use_eos,
+                      float* out);
+
 }  // namespace cst

@@ -73,6 +73,15 @@ void launch_cider_unclipped(const int64_t* hyps, int T, const int64_t* hyp_video
                             int use_eos, const int64_t* exclude, float* out,
                             hipStream_t stream);
 
+// cider_pairwise.hip: peer CIDEr-D (consensus / MBR decoding).  hyps (B * G, T):
+// every row against the G - 1 other rows of its pool of G; only the df hash table
+// is read.  peer_cider_supported: 2 <= G <= 64, 1 <= T <= 63 and G * (T + 1) <= 2048
+// (a pool's vectors fit one CU's LDS); the launcher throws outside it.
+bool peer_cider_supported(int64_t G, int64_t T);
+void launch_cider_pairwise(const int64_t* hyps, int T, int G, int B, const int64_t* ht_keys,
+                           const float* ht_vals, uint32_t ht_cap, float log_ref_len,
+                           int use_eos, float* out, hipStream_t stream);
+
 // sent_metrics.hip: sentence BLEU-4 / ROUGE-L of N hypotheses (T <= 64), one
 // wavefront each, against the tables of host/metric_host.h (Nv videos)
 void launch_bleu4(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,

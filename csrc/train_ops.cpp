@@ -243,8 +243,38 @@ static const int64_t* exclude_ptr(const c10::optional<at::Tensor>& exclude, int6
 // On-GPU CIDEr-D scores of N hypotheses.
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
                        double log_ref_len, int64_t use_eos, bool clipped,
-                       c10::optional<at::Tensor> exclude) {
+                       c10::optional<at::Tensor> exclude, int64_t group) {
   check_cuda(hyps, "hyps");
+  if (group != 0) {
+    // Peer mode (consensus / MBR decoding, kernels/cider_pairwise.hip): rows
+    // [k * group, (k + 1) * group) are one pool, every row is scored against the
+    // others of its pool.  Only the df hash table is read; hyp_video is ignored.
+    TORCH_CHECK(hyps.scalar_type() == at::kLong && hyps.dim() == 2, "hyps: int64 (N, T)");
+    const int64_t N = hyps.size(0), T = hyps.size(1);
+    TORCH_CHECK(group >= 2, "cider_score: group = ", group,
+                "; a peer pool has at least 2 rows (group = 0: reference tables)");
+    TORCH_CHECK(clipped && !(exclude.has_value() && exclude->defined()),
+                "cider_score: peer mode (group > 0) is CIDEr-D without exclude: clipped must be "
+                "True and exclude None");
+    TORCH_CHECK(N % group == 0, "cider_score: ", N, " rows are not whole pools of ", group);
+    TORCH_CHECK(peer_cider_supported(group, T), "cider_score: a pool of group = ", group,
+                " rows of T = ", T, " tokens is outside the peer kernel's limit: group <= 64, "
+                "1 <= T <= 63 and group * (T + 1) <= 2048 (64 rows of 31 tokens, 32 rows of 63)");
+    TORCH_CHECK(t.count("ht_keys") && t.count("ht_vals"), "tables: ht_keys and ht_vals");
+    const at::Tensor& hk = t["ht_keys"];
+    const at::Tensor& hv = t["ht_vals"];
+    check_cuda(hk, "ht_keys");
+    check_cuda(hv, "ht_vals");
+    TORCH_CHECK(hk.scalar_type() == at::kLong && hv.scalar_type() == at::kFloat &&
+                    hk.numel() == hv.numel() && hk.numel() > 0 &&
+                    (hk.numel() & (hk.numel() - 1)) == 0,
+                "df hash table: int64 keys and fp32 values of one power-of-two size");
+    at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
+    launch_cider_pairwise(hyps.data_ptr<int64_t>(), (int)T, (int)group, (int)(N / group),
+                          hk.data_ptr<int64_t>(), hv.data_ptr<float>(), (uint32_t)hk.numel(),
+                          (float)log_ref_len, (int)use_eos, out.data_ptr<float>(), cur_stream());
+    return out;
+  }
   check_cuda(hyp_video, "hyp_video");
   TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
               "int64 inputs");

@@ -136,6 +136,14 @@ def test_main(argv=None):
     opt = parse_opts(argv)
     ctx = init_distributed()
     setup_logging(opt, ctx.rank)
+    if opt.decode == 'mbr' and not opt.synthetic:
+        # consensus decoding scores under the TRAINING set's df table (the
+        # synthetic split carries its own); refused here, before the model is built
+        if not isinstance(opt.train_cached_tokens, str):
+            raise ValueError('--decode mbr needs the CIDEr-D document-frequency table of the '
+                             'training set: --train_cached_tokens')
+        from .prepro.ciderdf import load_packed_df
+        opt.mbr_df = load_packed_df(opt.train_cached_tokens)
     from .train.checkpoint import load_checkpoint
     ck = load_checkpoint(opt.model_file, 'cpu')
     copt = ck['opt']
@@ -150,6 +158,9 @@ def test_main(argv=None):
     loader = CaptionLoader(te, opt.test_batch_size, opt.test_seq_per_img, 'test', ctx.device)
     from .train.trainer import Trainer, check_val_scorer
     check_val_scorer(opt, loader)
+    if opt.decode == 'mbr' and opt.synthetic and te.df is None:
+        raise ValueError('--decode mbr needs a CIDEr-D document-frequency table; the '
+                         'synthetic split has none')
     assert opt.vocab_size == loader.get_vocab_size()
     assert opt.seq_length == loader.get_seq_length()
     assert list(opt.feat_dims) == list(loader.get_feat_dims())

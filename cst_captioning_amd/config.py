@@ -106,6 +106,17 @@ def build_parser():
         help='validation / test metrics: strings = decoded sentences through the Python '
              'scorers (reference route); tokens = token ids against the split\'s label table, '
              'on the GPU when the model runs there (ops/corpus_metrics.py)')
+    add('--decode', type=str, default='standard', choices=['standard', 'mbr'],
+        help='validation / test decoding: standard = greedy (--beam_size 1) or beam search; '
+             'mbr = consensus (minimum-Bayes-risk) decoding: the standard caption plus '
+             '--mbr_samples multinomial samples per video, every one scored against the others '
+             'under CIDEr-D (ops/mbr.py, on the GPU when the model runs there), the one that '
+             'agrees most returned.  Needs a CIDEr-D document-frequency table: the training '
+             "set's, or --train_cached_tokens for the test command")
+    add('--mbr_samples', type=int, default=20,
+        help='--decode mbr: multinomial samples per video beside the standard caption')
+    add('--mbr_temperature', type=float, default=1.0,
+        help='--decode mbr: sampling temperature of those samples')
     add('--consensus_scorer', type=str, default='file', choices=['file', 'tokens'],
         help='GT consensus scores of CST / WXE training: file = read --train_bcmrscores_pkl '
              '(prepro/evalscores.py); tokens = computed at start-up (when --use_cst 1) from the training label '

@@ -174,6 +174,8 @@ class CaptionModel(nn.Module):
 
     # -- greedy / multinomial decoding ----------------------------------------
     def sample(self, feats, opt={}):
+        if opt.get('decode', 'standard') == 'mbr':
+            return self.sample_mbr(feats, opt)[:2]
         beam_size = opt.get('beam_size', 1)
         if beam_size > 1:
             return self.sample_beam(feats, opt)
@@ -215,6 +217,49 @@ class CaptionModel(nn.Module):
             out, state = self._step(xt, ctx, state)
             logprobs = F.log_softmax(self.logit(out), dim=-1)
         return torch.stack(seq, 1), torch.stack(seq_lp, 1)
+
+    # -- consensus (minimum-Bayes-risk) decoding --------------------------------
+    @torch.no_grad()
+    def sample_mbr(self, feats, opt={}):
+        """The caption that agrees most with what the model itself says about
+        the video.  The pool of video ``k``: row 0 the standard decode (greedy
+        for ``beam_size`` 1, else beam search), rows 1..N multinomial samples
+        (``N = opt['mbr_samples']``, ``opt['mbr_temperature']``, one expanded
+        call), all padded with 0 to one width; ``G = N + 1``.  Every row is
+        scored against its peers by ``opt['mbr_scorer']``
+        (:class:`..ops.mbr.PeerCiderD`) and the best row is returned, index 0
+        winning ties.  Returns ``(seq (B, T), logprobs (B, T), info)`` with
+        ``info = {'pool': (B, G, T), 'scores': (B, G), 'best': (B,)}``.  The
+        sampling seeds come from torch's generator.  Pooling, scoring and
+        selection add no host synchronisation to what the decodes do themselves
+        (the fused engine's have none, the torch path's loops test for an early
+        end on the host every step)."""
+        scorer = opt.get('mbr_scorer', None)
+        if scorer is None:
+            raise ValueError("decode 'mbr' needs opt['mbr_scorer'] (ops.mbr.PeerCiderD)")
+        N = int(opt.get('mbr_samples', 20))
+        if N < 1:
+            raise ValueError('mbr_samples must be at least 1, got %d' % N)
+        std = {k: v for k, v in opt.items() if not k.startswith('mbr_') and k != 'decode'}
+        std.update(sample_max=1, expand_feat=0)
+        seq0, lp0 = self.sample(feats, std)
+        prev = self.seq_per_img
+        self.set_seq_per_img(N)
+        try:
+            seqs, lps = self.sample(feats, {'sample_max': 0, 'expand_feat': 1, 'beam_size': 1,
+                                            'temperature': float(opt.get('mbr_temperature',
+                                                                         1.0))})
+        finally:
+            self.set_seq_per_img(prev)
+        B, G = seq0.size(0), N + 1
+        T = max(seq0.size(1), seqs.size(1))
+        pad = lambda x: F.pad(x, (0, T - x.size(1)))
+        pool = torch.cat([pad(seq0).unsqueeze(1), pad(seqs).view(B, N, T)], 1)
+        lps = torch.cat([pad(lp0.float()).unsqueeze(1), pad(lps.float()).view(B, N, T)], 1)
+        best, scores = scorer.select(pool.reshape(B * G, T), G)
+        pick = best.view(B, 1, 1).expand(B, 1, T)
+        info = {'pool': pool, 'scores': scores, 'best': best}
+        return pool.gather(1, pick).squeeze(1), lps.gather(1, pick).squeeze(1), info
 
     # -- beam search (batched over videos, reference semantics) ----------------
     def sample_beam(self, feats, opt={}):

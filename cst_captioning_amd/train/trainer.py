@@ -195,6 +195,10 @@ class Trainer:
         # its first scoring; that the split can be scored is checked up front
         self._corpus_scorers = {}
         self.check_val_scorer(val_loader)
+        # --decode mbr: the peer scorer of consensus decoding, built at set-up
+        # from the training set's df table (opt.mbr_df where the caller loaded
+        # one: the test command) -- never from the evaluated split's labels
+        self.mbr_scorer = self._build_mbr_scorer()
         # HIP-graph step (see graph_step): captured step per schedule key
         self._graph = None
         self._graph_key = None
@@ -800,6 +804,43 @@ class Trainer:
             logger.info('%s', '\t'.join('{}: {}'.format(k, v) for k, v in items))
 
     # ----------------------------------------------------------- validate ---
+    def _build_mbr_scorer(self):
+        opt = self.opt
+        if getattr(opt, 'decode', 'standard') != 'mbr':
+            return None
+        df = getattr(opt, 'mbr_df', None)
+        if df is None and self.train_loader is not None:
+            df = self.train_loader.ds.df
+        if df is None:
+            raise ValueError('--decode mbr scores captions under CIDEr-D and needs a '
+                             'document-frequency table: the training dataset has none '
+                             '(--train_cached_tokens)')
+        if int(opt.mbr_samples) < 1:
+            raise ValueError('--mbr_samples must be at least 1, got %d' % opt.mbr_samples)
+        if not float(opt.mbr_temperature) > 0:
+            raise ValueError('--mbr_temperature must be positive, got %r' % opt.mbr_temperature)
+        from ..ops.mbr import PeerCiderD
+        return PeerCiderD(df, use_eos=opt.use_eos, device=self.device, backend='auto')
+
+    def decode_opts(self):
+        """The options of the validation / test decode (``model.sample``)."""
+        o = {'beam_size': self.opt.beam_size}
+        if self.mbr_scorer is not None:
+            o.update(decode='mbr', mbr_samples=int(self.opt.mbr_samples),
+                     mbr_temperature=float(self.opt.mbr_temperature),
+                     mbr_scorer=self.mbr_scorer)
+        return o
+
+    def _decode(self, feats):
+        """(seq, logprobs, peer score of the returned row or None), on the
+        device."""
+        o = self.decode_opts()
+        if self.mbr_scorer is None:
+            seq, logseq = self.model.sample(feats, o)
+            return seq, logseq, None
+        seq, logseq, info = self.model.sample_mbr(feats, o)
+        return seq, logseq, info['scores'].gather(1, info['best'].view(-1, 1)).view(-1)
+
     def check_val_scorer(self, loader):
         check_val_scorer(self.opt, loader)
 
@@ -830,13 +871,16 @@ class Trainer:
         return loss, gt_seq, gt_lp
 
     @staticmethod
-    def _val_entries(local, ii, ids, sents, avg):
+    def _val_entries(local, ii, ids, sents, avg, mbr=None):
         """Appends batch ``ii``'s prediction entries (``avg``: the rows'
-        avglogp, or None) to ``local['pred']``."""
+        avglogp, or None; ``mbr``: with --decode mbr the rows' peer scores) to
+        ``local['pred']``."""
         for jj, sent in enumerate(sents):
             e = {'image_id': ids[jj], 'caption': sent}
             if avg is not None:
                 e['avglogp'] = avg[jj]
+            if mbr is not None:
+                e['mbr_score'] = float(mbr[jj])
             local['pred'].append((ii, jj, e))
             logger.debug('[%d] video %s: %s', jj, e['image_id'], sent)
 
@@ -892,15 +936,18 @@ class Trainer:
         m.set_seq_per_img(S)
         want_logp = opt.output_logp == 1
         its, seqs, logseqs, vids, ids, losses, gt_pairs = [], [], [], [], [], [], []
+        peer = []  # (--decode mbr: the returned rows' peer scores, on the device)
         for ii in range(ctx.rank, n_iters, ctx.world_size):  # C4: batches sharded over ranks
             data = loader.get_batch_at(ii)
             loss, gt_seq, gt_lp = self._val_loss(data)
             losses.append(loss.detach().reshape(()))
             if want_logp:
                 gt_pairs.append((gt_seq, gt_lp))
-            seq, logseq = m.sample(data['feats'], {'beam_size': opt.beam_size})
+            seq, logseq, sc = self._decode(data['feats'])
             its.append(ii)
             seqs.append(seq)
+            if sc is not None:
+                peer.append(sc)
             vids.append(data['vids'])
             ids.append(data['ids'])
             if want_logp:
@@ -913,6 +960,7 @@ class Trainer:
         seq_dev = torch.cat(seqs) if seqs else torch.zeros(0, 0, dtype=torch.long)
         seq_host = seq_dev.cpu().numpy()
         loss_host = torch.stack(losses).cpu().tolist() if losses else []
+        peer_host = torch.cat(peer).cpu().numpy() if peer else None
         vid_host = np.concatenate(vids) if vids else np.zeros(0, np.int64)
         sents = decode_sequence(loader.get_vocab(), seq_host)
         logseq_host = None
@@ -928,7 +976,8 @@ class Trainer:
             # run on into the padding)
             avg = None if logseq_host is None else compute_avglogp(
                 seq_host[row:row + n, :w], logseq_host[row:row + n, :w])
-            self._val_entries(local, ii, batch_ids, sents[row:row + n], avg)
+            self._val_entries(local, ii, batch_ids, sents[row:row + n], avg,
+                              None if peer_host is None else peer_host[row:row + n])
             row += n
         for ii, (gt_seq, gt_lp) in zip(its, gt_pairs):
             local['gt_avglogp'].append(
@@ -973,11 +1022,12 @@ class Trainer:
                 if opt.output_logp == 1:
                     local['gt_avglogp'].append(
                         (ii, compute_avglogp(gt_seq.cpu().numpy(), gt_lp.cpu().numpy())))
-            seq, logseq = m.sample(data['feats'], {'beam_size': opt.beam_size})
+            seq, logseq, sc = self._decode(data['feats'])
             seq, logseq = seq.cpu().numpy(), logseq.cpu().numpy()
             sents = decode_sequence(loader.get_vocab(), seq)
             avg = compute_avglogp(seq, logseq) if opt.output_logp == 1 else None
-            self._val_entries(local, ii, data['ids'], sents, avg)
+            self._val_entries(local, ii, data['ids'], sents, avg,
+                              None if sc is None else sc.cpu().numpy())
 
         def metrics(predictions, gathered):
             if not loader.has_label:
