@@ -73,6 +73,9 @@ USE_EOS?=0
 # table (compute_evalscores writes the same file layout; train computes them at
 # start-up and reads no file)
 CONSENSUS_SCORER?=file
+# RL reward as a weighted sum of metrics, e.g. REWARD_MIX=CIDEr:1,Bleu_4:5,ROUGE_L:5
+# (empty: the reward is EVAL_METRIC); passed to train only when set
+REWARD_MIX?=
 # validation / test decoding: standard (greedy or beam), or mbr = consensus
 # decoding over the standard caption + MBR_SAMPLES samples at MBR_TEMPERATURE
 DECODE?=standard
@@ -176,6 +179,7 @@ TRAIN_OPT=--beam_size $(BEAM_SIZE) --max_patience $(MAX_PATIENCE) --eval_metric 
 	--use_cst $(USE_CST) --scb_captions $(SCB_CAPTIONS) --scb_baseline $(SCB_BASELINE) \
 	--loglevel $(LOGLEVEL) --model_type $(MODEL_TYPE) --use_eos $(USE_EOS) \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
+	$(if $(REWARD_MIX),--reward_mix $(REWARD_MIX)) \
 	--model_file $@ --start_from $(START_FROM) --result_file $(basename $@)_test.json \
 	2>&1 | tee $(basename $@).log
 

@@ -240,9 +240,36 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "METEOR alignment statistics per hypothesis on the GPU: (N, 6) int32, (N) fp64");
   m.def("meteor_stats_cpu", &cst::meteor_stats_cpu, py::arg("hyps"), py::arg("hyp_video"),
         py::arg("tables"), py::arg("stem_ids"), py::arg("exclude") = py::none());
-  m.def("metric_score", &cst::metric_score, py::arg("metric"), py::arg("hyps"),
-        py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
-        py::arg("exclude") = py::none(), "Bleu_4 | ROUGE_L sentence scores on the GPU (one launch, capturable)");
+  // metric = "mix" (--reward_mix; kernels/reward_mix.hip): weights = (w_c, w_b, w_r)
+  // over CIDEr-D, Bleu_4, ROUGE_L; tables = the sentence-metric tables and
+  // cider_tables / log_ref_len those of cider_score, each None when its metrics
+  // have weight 0; returns [out (N), parts (N, 3)] of ONE launch
+  // (cst::reward_mix_score).  The extension's set of bound names is pinned, so
+  // the mixed reward is a mode of this op, as peer mode is one of cider_score.
+  m.def(
+      "metric_score",
+      [](const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
+         c10::optional<std::map<std::string, at::Tensor>> tables, int64_t use_eos,
+         c10::optional<at::Tensor> exclude,
+         c10::optional<std::map<std::string, at::Tensor>> cider_tables, double log_ref_len,
+         c10::optional<std::vector<double>> weights) -> py::object {
+        if (metric == "mix") {
+          TORCH_CHECK(weights.has_value(), "metric_score: metric mix needs weights");
+          TORCH_CHECK(!(exclude.has_value() && exclude->defined()),
+                      "metric_score: metric mix takes no exclude");
+          return py::cast(cst::reward_mix_score(hyps, hyp_video, cider_tables, tables,
+                                                log_ref_len, use_eos, *weights));
+        }
+        TORCH_CHECK(tables.has_value(), "metric_score: tables must be given");
+        TORCH_CHECK(!weights.has_value() && !cider_tables.has_value(),
+                    "metric_score: weights / cider_tables go with metric mix only");
+        return py::cast(cst::metric_score(metric, hyps, hyp_video, *tables, use_eos, exclude));
+      },
+      py::arg("metric"), py::arg("hyps"), py::arg("hyp_video"), py::arg("tables"),
+      py::arg("use_eos"), py::arg("exclude") = py::none(), py::arg("cider_tables") = py::none(),
+      py::arg("log_ref_len") = 0.0, py::arg("weights") = py::none(),
+      "Bleu_4 | ROUGE_L sentence scores on the GPU, or their weighted mix with CIDEr-D "
+      "(metric mix); one launch, capturable");
   m.def("metric_score_cpu", &cst::metric_score_cpu, py::arg("metric"), py::arg("hyps"),
         py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
         py::arg("exclude") = py::none());

@@ -99,6 +99,11 @@ std::vector<at::Tensor> meteor_stats(at::Tensor hyps, at::Tensor hyp_video,
 at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
                         std::map<std::string, at::Tensor> t, int64_t use_eos,
                         c10::optional<at::Tensor> exclude);
+std::vector<at::Tensor> reward_mix_score(
+    at::Tensor hyps, at::Tensor hyp_video,
+    c10::optional<std::map<std::string, at::Tensor>> cider_tables,
+    c10::optional<std::map<std::string, at::Tensor>> sent_tables, double log_ref_len,
+    int64_t use_eos, std::vector<double> weights);
 at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                           at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
                           double b1, double b2, double eps, double clip, double gscale,

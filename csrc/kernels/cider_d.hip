@@ -23,8 +23,11 @@
 // reference e of the hypothesis' video (excluded_ref, cider_common.h) and the
 // mean divides by the references used.
 // Deterministic: fixed-order wave/block reductions, no atomics.
+// Steps 2-5 are functions of reward_bodies.h, which reward_mix_kernel
+// (reward_mix.hip) calls too.
 #include "../common.h"
 #include "../cider_common.h"
+#include "reward_bodies.h"
 
 namespace cst {
 
@@ -53,6 +56,8 @@ __device__ __forceinline__ void cider_body(
   const int w = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
   const int hyp = blockIdx.x;
+  const CiderTables tab = {ht_keys, ht_vals, ht_cap, vid_ref_off, ref_ng_off,
+                           ref_norm, ref_len, ng_key,  ng_val,     log_ref_len};
 
   // -- 1. compaction (wave 0) ----------------------------------------------------
   if (w == 0) {
@@ -62,87 +67,27 @@ __device__ __forceinline__ void cider_body(
   __syncthreads();
   const int W = s_W;
   // -- 2. packed n-gram keys: wave n builds the order-(n+1) keys ------------------
-  {
-    const int n = w, cnt = W - n;
-    uint64_t key = 0;
-    if (lane < cnt) {
-      for (int i = 0; i <= n; ++i) key |= (uint64_t)(s_tok[lane + i] + 1) << (16 * i);
-    }
-    s_key[n][lane] = key;
-  }
+  s_key[w][lane] = ngram_key<false>(s_tok, W, w, lane);
   __syncthreads();
   // -- 3. tf (first occurrence), idf, per-order norm: wave n handles order n+1 ----
   {
-    const int n = w, cnt = W - n;
-    float v = 0.f;
-    if (lane < cnt) {
-      const uint64_t key = s_key[n][lane];
-      int tf = 0;
-      bool first = true;
-      for (int j = 0; j < cnt; ++j) {
-        const bool eq = s_key[n][j] == key;
-        tf += eq;
-        first = first && !(eq && j < lane);
-      }
-      if (first) {
-        const float df = df_lookup(ht_keys, ht_vals, ht_cap, key);
-        v = (float)tf * (log_ref_len - __logf(fmaxf(1.f, df)));
-      }
-    }
-    s_val[n][lane] = v;
+    const float v = cider_hyp_value(tab, s_key[w], W - w, lane);
+    s_val[w][lane] = v;
     const float nrm = sqrtf(wave_sum(v * v));
-    if (lane == 0) s_norm[n] = nrm;
+    if (lane == 0) s_norm[w] = nrm;
   }
   __syncthreads();
-  const float len_h = (float)max(W - 1, 0);
-  float norm_h[4] = {s_norm[0], s_norm[1], s_norm[2], s_norm[3]};
+  const float norm_h[4] = {s_norm[0], s_norm[1], s_norm[2], s_norm[3]};
 
   // -- 4. references, split over the 4 waves --------------------------------------
   const int v = (int)hyp_video[hyp];
   const int r0 = vid_ref_off[v], r1 = vid_ref_off[v + 1];
   const int ex = excluded_ref(exclude, hyp, r0, r1);  // (leave-one-out: -1 = none)
-  float total = 0.f;
-  for (int r = r0 + w; r < r1; r += 4) {
-    if (r == ex) continue;  // (wave-uniform)
-    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f, acc3 = 0.f;
-    const int g0 = ref_ng_off[r], g1 = ref_ng_off[r + 1];
-    for (int g = g0 + lane; g < g1; g += 64) {
-      const uint64_t key = (uint64_t)ng_key[g];
-      const float vr = ng_val[g];
-      const int n = ngram_order(key) - 1;
-      const int cnt = W - n;
-      float c = 0.f;
-      for (int j = 0; j < cnt; ++j) {
-        if (s_key[n][j] == key) c += (CLIPPED ? fminf(s_val[n][j], vr) : s_val[n][j]) * vr;
-      }
-      acc0 += n == 0 ? c : 0.f;
-      acc1 += n == 1 ? c : 0.f;
-      acc2 += n == 2 ? c : 0.f;
-      acc3 += n == 3 ? c : 0.f;
-    }
-    const float acc[4] = {wave_sum(acc0), wave_sum(acc1), wave_sum(acc2), wave_sum(acc3)};
-    float pen = 1.f;
-    if (CLIPPED) {
-      const float delta = len_h - (float)ref_len[r];
-      pen = __expf(-(delta * delta) / 72.f);
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const float nr = ref_norm[r * 4 + n];
-      float val = acc[n];
-      if (norm_h[n] != 0.f && nr != 0.f) val /= (norm_h[n] * nr);
-      s += val * pen;
-    }
-    total += s;
-  }
+  const float total = cider_refs<CLIPPED>(tab, s_key, s_val, W, norm_h, r0, r1, ex, w, 4, lane);
   if (lane == 0) s_part[w] = total;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const int nref = r1 - r0 - (ex >= 0 ? 1 : 0);  // (the references used)
-    const float t4 = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
-    out[hyp] = nref > 0 ? 10.f * t4 / (4.f * (float)nref) : 0.f;
-  }
+  // (the mean divides by the references used)
+  if (threadIdx.x == 0) out[hyp] = cider_final(s_part, r1 - r0 - (ex >= 0 ? 1 : 0));
 }
 
 __global__ __launch_bounds__(256) void cider_d_kernel(

@@ -15,24 +15,18 @@
 // Deterministic: integer counts, fixed-order wave reductions, no atomics, no
 // communication between waves or workgroups.  The final formulas are evaluated
 // in double by one lane and rounded once to fp32.
+//
+// The bodies (keys, term frequencies, the reference loops and the final
+// formulas) are functions of reward_bodies.h, which reward_mix_kernel
+// (reward_mix.hip) calls too; the kernels here do the compaction and own the LDS.
 #include "../common.h"
 #include "../cider_common.h"
+#include "reward_bodies.h"
 
 namespace cst {
 
 constexpr int SM_MAXT = 64;
 constexpr int SM_WAVES = 4;  // hypotheses per block
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // BLEU-4.  Per wave:
 //   1. compaction (compact_hypothesis, shared with cider_d_kernel);
@@ -75,89 +69,17 @@ __global__ __launch_bounds__(64 * SM_WAVES) void bleu4_kernel(
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    uint64_t key = 0;
-    if (lane < W - n) {
-      bool ok = true;
-#pragma unroll
-      for (int i = 0; i <= n; ++i) {
-        const int t = s_tok[w][lane + i];
-        ok = ok && t >= 0 && t < 65535;
-        key |= (uint64_t)((t + 1) & 0xffff) << (16 * i);
-      }
-      if (!ok) key = 0;
-    }
-    s_key[w][n][lane] = key;
-  }
+  for (int n = 0; n < 4; ++n) s_key[w][n][lane] = ngram_key<true>(s_tok[w], W, n, lane);
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 #pragma unroll
-  for (int n = 0; n < 4; ++n) {
-    const int cnt = W - n;
-    int tf = 0;
-    if (lane < cnt) {
-      const uint64_t key = s_key[w][n][lane];
-      bool first = true;
-      for (int j = 0; j < cnt; ++j) {
-        const bool eq = s_key[w][n][j] == key;
-        tf += eq;
-        first = first && !(eq && j < lane);
-      }
-      if (!first) tf = 0;
-    }
-    s_tf[w][n][lane] = tf;
-  }
+  for (int n = 0; n < 4; ++n) s_tf[w][n][lane] = first_tf(s_key[w][n], W - n, lane);
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 
-  const int64_t v64 = hyp_video[hyp];
-  const bool vok = v64 >= 0 && v64 < Nv;  // (a video outside the tables scores 0)
-  const int v = vok ? (int)v64 : 0;
-  const int r0 = vid_ref_off[v], r1 = vok ? vid_ref_off[v + 1] : r0;
-  // leave-one-out: the in-video index of the reference left out, -1 for none
-  // (wave-uniform; only then are ng_cnt2 / ng_arg read)
-  const int ex = excluded_ref(exclude, hyp, r0, r1);
-  const int e = ex >= 0 ? ex - r0 : -1;
-  int c0 = 0, c1 = 0, c2 = 0, c3 = 0;
-  const int g0 = vid_ng_off[v], g1 = vok ? vid_ng_off[v + 1] : g0;
-  for (int g = g0 + lane; g < g1; g += 64) {
-    const uint64_t key = (uint64_t)ng_key[g];
-    int clip = ng_cnt[g];
-    if (e >= 0 && ng_arg[g] == e) clip = ng_cnt2[g];  // (0: adds nothing)
-    const int n = ngram_order(key) - 1;
-    const int cnt = W - n;
-    int c = 0;
-    for (int j = 0; j < cnt; ++j) {
-      if (s_key[w][n][j] == key) c += min(s_tf[w][n][j], clip);
-    }
-    c0 += n == 0 ? c : 0;
-    c1 += n == 1 ? c : 0;
-    c2 += n == 2 ? c : 0;
-    c3 += n == 3 ? c : 0;
-  }
-  const int correct[4] = {wave_sum_i(c0), wave_sum_i(c1), wave_sum_i(c2), wave_sum_i(c3)};
-  int best = 0x7fffffff;
-  for (int r = r0 + lane; r < r1; r += 64) {
-    const int lr = ref_len[r];
-    if (r != ex) best = min(best, (abs(lr - W) << 8) | lr);
-  }
-  best = wave_min_i(best);
-  if (lane == 0) {
-    float res = 0.f;
-    if (r1 > r0) {
-      const double tiny = 1e-15, small = 1e-9;
-      const int rlen = best & 0xff;
-      double b = 1.0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        b *= ((double)correct[k] + tiny) / ((double)max(0, W - k) + small);
-      double s = pow(b, 0.25);
-      const double ratio = ((double)W + tiny) / ((double)rlen + small);
-      if (ratio < 1.0) s *= exp(1.0 - 1.0 / ratio);
-      res = (float)s;
-    }
-    out[hyp] = res;
-  }
+  const BleuTables tab = {Nv, vid_ref_off, ref_len, vid_ng_off, ng_key, ng_cnt, ng_cnt2, ng_arg};
+  const float res = bleu4_refs(tab, s_key[w], s_tf[w], W, hyp, hyp_video, exclude, lane);
+  if (lane == 0) out[hyp] = res;
 }
 
 // ROUGE-L.  Per wave: compaction, then lane j keeps hypothesis token j (-1 past
@@ -189,55 +111,9 @@ __global__ __launch_bounds__(64 * SM_WAVES) void rouge_l_kernel(
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   const int htok = lane < W ? s_tok[w][lane] : -1;
-
-  const int64_t v64 = hyp_video[hyp];
-  const bool vok = v64 >= 0 && v64 < Nv;  // (a video outside the tables scores 0)
-  const int v = vok ? (int)v64 : 0;
-  const int r0 = vid_ref_off[v], r1 = vok ? vid_ref_off[v + 1] : r0;
-  int best_l = 0;             // max lcs (precision: the denominator len_h is shared)
-  int rec_l = 0, rec_n = 1;   // max lcs / len_r as a fraction
-  // leave-one-out: the loop walks the references other than `ex` (-1: all of
-  // them); `r` is the reference being processed, `rn` the one after it, both
-  // stepped over `ex`, so the prefetch never loads the excluded row
-  const int ex = excluded_ref(exclude, hyp, r0, r1);
-  int o0 = 0, o1 = 0, nxt = -2;
-  int r = r0 == ex ? r0 + 1 : r0;
-  if (r < r1) {
-    o0 = ref_tok_off[r];
-    o1 = ref_tok_off[r + 1];
-    nxt = lane < min(o1 - o0, 64) ? ref_tok[o0 + lane] : -2;
-  }
-  while (r < r1) {
-    const int n = min(o1 - o0, 64);
-    const int rtok = nxt;
-    const int rn = r + 1 == ex ? r + 2 : r + 1;
-    if (rn < r1) {  // prefetch the next reference
-      o0 = ref_tok_off[rn];
-      o1 = ref_tok_off[rn + 1];
-      nxt = lane < min(o1 - o0, 64) ? ref_tok[o0 + lane] : -2;
-    }
-    r = rn;
-    uint64_t V = ~0ull;
-    for (int a = 0; a < n; ++a) {
-      const int c = __builtin_amdgcn_readlane(rtok, a);
-      const uint64_t M = __ballot(htok == c);
-      const uint64_t U = V & M;
-      V = (V + U) | (V - U);
-    }
-    const int l = __popcll(~V);
-    best_l = max(best_l, l);
-    if (n > 0 && l * rec_n > rec_l * n) rec_l = l, rec_n = n;
-  }
-  if (lane == 0) {
-    float res = 0.f;
-    if (W > 0 && best_l > 0 && rec_l > 0) {
-      const double beta = 1.2, b2 = beta * beta;
-      const double p = (double)best_l / (double)W;
-      const double rc = (double)rec_l / (double)rec_n;
-      res = (float)(((1.0 + b2) * p * rc) / (rc + b2 * p));
-    }
-    out[hyp] = res;
-  }
+  const RougeTables tab = {Nv, vid_ref_off, ref_tok_off, ref_tok};
+  const float res = rouge_l_refs(tab, htok, W, hyp, hyp_video, exclude, lane);
+  if (lane == 0) out[hyp] = res;
 }
 
 void launch_bleu4(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,

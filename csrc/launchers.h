@@ -94,6 +94,32 @@ void launch_rouge_l(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
                     const int32_t* ref_tok, int use_eos, const int64_t* exclude, float* out,
                     hipStream_t stream);
 
+// reward_mix.hip: w_c * CIDEr-D + w_b * BLEU-4 + w_r * ROUGE-L of N hypotheses
+// in one launch: out (N), parts (N, 3) = the three scores (0 where the weight
+// is 0).  The tables of a metric of weight 0 may be null.  T <= 64 (63 with
+// CIDEr-D).
+struct MixCiderArgs {  // (the tables of launch_cider_d, Nv videos)
+  int Nv = 0;
+  const int64_t* ht_keys = nullptr;
+  const float* ht_vals = nullptr;
+  uint32_t ht_cap = 0;
+  const int32_t *vid_ref_off = nullptr, *ref_ng_off = nullptr;
+  const float* ref_norm = nullptr;
+  const int32_t* ref_len = nullptr;
+  const int64_t* ng_key = nullptr;
+  const float* ng_val = nullptr;
+  float log_ref_len = 0.f;
+};
+struct MixSentArgs {  // (the tables of launch_bleu4 / launch_rouge_l)
+  int Nv = 0;
+  const int32_t *vid_ref_off = nullptr, *ref_len = nullptr, *vid_ng_off = nullptr;
+  const int64_t* ng_key = nullptr;
+  const int32_t *ng_cnt = nullptr, *ref_tok_off = nullptr, *ref_tok = nullptr;
+};
+void launch_reward_mix(const int64_t* hyps, int T, const int64_t* hyp_video, int N,
+                       const MixCiderArgs& c, const MixSentArgs& s, int use_eos, float w_c,
+                       float w_b, float w_r, float* out, float* parts, hipStream_t stream);
+
 // corpus_metrics.hip: per-hypothesis statistics of corpus BLEU (10 x int32) and
 // METEOR (6 x int32 + the fp64 segment score), one wavefront each (T <= 64)
 void launch_bleu_stats(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,

@@ -348,6 +348,103 @@ at::Tensor metric_score(const std::string& metric, at::Tensor hyps, at::Tensor h
   return out;
 }
 
+// Mixed-metric reward (kernels/reward_mix.hip): weights = (w_c, w_b, w_r) over
+// CIDEr-D, BLEU-4, ROUGE-L; returns {out (N), parts (N, 3)}.  The tables of a
+// metric of weight 0 are not read and may be None.  One launch, no allocation
+// besides the results and no synchronisation: capturable.  Limits (checked
+// here, before the launch): T <= 64, T <= 63 with CIDEr-D; token ids are those
+// of the tables' builders (<= 65,534 in the references; a larger hypothesis
+// token matches nothing, as in bleu4_kernel).
+std::vector<at::Tensor> reward_mix_score(
+    at::Tensor hyps, at::Tensor hyp_video,
+    c10::optional<std::map<std::string, at::Tensor>> cider_tables,
+    c10::optional<std::map<std::string, at::Tensor>> sent_tables, double log_ref_len,
+    int64_t use_eos, std::vector<double> weights) {
+  check_cuda(hyps, "hyps");
+  check_cuda(hyp_video, "hyp_video");
+  TORCH_CHECK(hyps.dim() == 2 && hyp_video.dim() == 1 && hyp_video.size(0) == hyps.size(0),
+              "hyps (N, T) and hyp_video (N)");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyp_video.scalar_type() == at::kLong,
+              "int64 inputs");
+  TORCH_CHECK(hyps.is_contiguous() && hyp_video.is_contiguous(), "contiguous inputs");
+  TORCH_CHECK(weights.size() == 3, "reward_mix_score: weights = (CIDEr, Bleu_4, ROUGE_L)");
+  for (double w : weights)
+    TORCH_CHECK(std::isfinite(w) && w >= 0.0, "reward_mix_score: weight ", w,
+                " is negative or not finite");
+  const float w_c = (float)weights[0], w_b = (float)weights[1], w_r = (float)weights[2];
+  TORCH_CHECK(w_c != 0.f || w_b != 0.f || w_r != 0.f, "reward_mix_score: all weights are zero");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  const int64_t maxT = w_c != 0.f ? 63 : 64;
+  TORCH_CHECK(T <= maxT, "hypotheses of ", T, " tokens; at most ", maxT,
+              " are supported", w_c != 0.f ? " with CIDEr-D in the mix" : "");
+  MixCiderArgs c;
+  MixSentArgs s;
+  if (w_c != 0.f) {
+    TORCH_CHECK(cider_tables.has_value(), "reward_mix_score: CIDEr has a weight but no tables");
+    auto& t = *cider_tables;
+    for (const char* k : {"ht_keys", "ht_vals", "vid_ref_off", "ref_ng_off", "ref_norm", "ref_len",
+                          "ng_key", "ng_val"}) {
+      TORCH_CHECK(t.count(k), "CIDEr-D tables lack ", k);
+      check_cuda(t[k], k);
+      const std::string n(k);
+      const auto want = (n == "ht_keys" || n == "ng_key") ? at::kLong
+                        : (n == "ht_vals" || n == "ref_norm" || n == "ng_val") ? at::kFloat
+                                                                               : at::kInt;
+      TORCH_CHECK(t[k].scalar_type() == want && t[k].is_contiguous(), "CIDEr-D table ", k,
+                  " has the wrong dtype");
+    }
+    const int64_t cap = t["ht_keys"].numel(), nref = t["ref_len"].numel();
+    TORCH_CHECK(cap > 0 && (cap & (cap - 1)) == 0 && t["ht_vals"].numel() == cap,
+                "df hash table: int64 keys and fp32 values of one power-of-two size");
+    TORCH_CHECK(t["vid_ref_off"].numel() >= 1 && t["ref_ng_off"].numel() == nref + 1 &&
+                    t["ref_norm"].numel() == 4 * nref &&
+                    t["ng_key"].numel() == t["ng_val"].numel(),
+                "CIDEr-D tables are inconsistent");
+    c.Nv = (int)t["vid_ref_off"].numel() - 1;
+    c.ht_keys = t["ht_keys"].data_ptr<int64_t>();
+    c.ht_vals = t["ht_vals"].data_ptr<float>();
+    c.ht_cap = (uint32_t)cap;
+    c.vid_ref_off = t["vid_ref_off"].data_ptr<int32_t>();
+    c.ref_ng_off = t["ref_ng_off"].data_ptr<int32_t>();
+    c.ref_norm = t["ref_norm"].data_ptr<float>();
+    c.ref_len = t["ref_len"].data_ptr<int32_t>();
+    c.ng_key = t["ng_key"].data_ptr<int64_t>();
+    c.ng_val = t["ng_val"].data_ptr<float>();
+    c.log_ref_len = (float)log_ref_len;
+  }
+  if (w_b != 0.f || w_r != 0.f) {
+    TORCH_CHECK(sent_tables.has_value(),
+                "reward_mix_score: Bleu_4 / ROUGE_L has a weight but no tables");
+    auto& t = *sent_tables;
+    for (const char* k : {"vid_ref_off", "ref_len", "vid_ng_off", "ng_key", "ng_cnt",
+                          "ref_tok_off", "ref_tok"}) {
+      TORCH_CHECK(t.count(k), "metric tables lack ", k);
+      check_cuda(t[k], k);
+      TORCH_CHECK(t[k].scalar_type() == (std::string(k) == "ng_key" ? at::kLong : at::kInt) &&
+                      t[k].is_contiguous(),
+                  "metric table ", k, " has the wrong dtype");
+    }
+    s.Nv = (int)t["vid_ref_off"].numel() - 1;
+    TORCH_CHECK(s.Nv >= 0 && t["vid_ng_off"].numel() == s.Nv + 1 &&
+                    t["ref_tok_off"].numel() == t["ref_len"].numel() + 1 &&
+                    t["ng_cnt"].numel() == t["ng_key"].numel(),
+                "metric tables are inconsistent");
+    s.vid_ref_off = t["vid_ref_off"].data_ptr<int32_t>();
+    s.ref_len = t["ref_len"].data_ptr<int32_t>();
+    s.vid_ng_off = t["vid_ng_off"].data_ptr<int32_t>();
+    s.ng_key = t["ng_key"].data_ptr<int64_t>();
+    s.ng_cnt = t["ng_cnt"].data_ptr<int32_t>();
+    s.ref_tok_off = t["ref_tok_off"].data_ptr<int32_t>();
+    s.ref_tok = t["ref_tok"].data_ptr<int32_t>();
+  }
+  at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
+  at::Tensor parts = at::empty({N, 3}, hyps.options().dtype(at::kFloat));
+  launch_reward_mix(hyps.data_ptr<int64_t>(), (int)T, hyp_video.data_ptr<int64_t>(), (int)N, c, s,
+                    (int)use_eos, w_c, w_b, w_r, out.data_ptr<float>(), parts.data_ptr<float>(),
+                    cur_stream());
+  return {out, parts};
+}
+
 // Validation scorer (kernels/corpus_metrics.hip): per-hypothesis statistics of
 // corpus BLEU ((N, 10) int32) or METEOR ((N, 6) int32 and the (N) fp64 segment
 // scores) against the tables of metric_build_tables (METEOR: built with stem

@@ -38,6 +38,9 @@ def load_splits(opt):
     if tokens and opt.train_bcmrscores_pkl:
         raise ValueError('--consensus_scorer tokens computes the consensus scores itself; '
                          '--train_bcmrscores_pkl must not be given with it')
+    if getattr(opt, 'reward_mix', ''):
+        from .ops.reward_mix import check_consensus_route
+        check_consensus_route(opt)
     if opt.synthetic:
         n = opt.synthetic_videos or None
         return make_splits(opt.synthetic, vocab_size=opt.synthetic_vocab,

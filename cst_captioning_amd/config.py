@@ -15,6 +15,18 @@ import argparse
 import sys
 
 
+def reward_mix_arg(spec):
+    """``--reward_mix``: '' (off) or a specification ops/reward_mix.py accepts."""
+    if spec == '':
+        return spec
+    from .ops.reward_mix import parse_reward_mix
+    try:
+        parse_reward_mix(spec)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return spec
+
+
 def build_parser():
     p = argparse.ArgumentParser(
         description='MI355X-native consensus/self-critical video captioning trainer')
@@ -102,6 +114,12 @@ def build_parser():
              'accumulation / master weights); fp32 = PyTorch path in fp32')
     add('--reward_device', type=str, default='gpu', choices=['gpu', 'cpu'],
         help='CIDEr-D reward: on-GPU HIP kernel, or the CPU scorer (reference semantics)')
+    add('--reward_mix', type=reward_mix_arg, default='', metavar='METRIC:WEIGHT[,...]',
+        help='RL reward = weighted sum of sentence metrics, e.g. CIDEr:1,Bleu_4:5,ROUGE_L:5 '
+             '(CIDEr = CIDEr-D on its x10 scale, Bleu_4, ROUGE_L; non-negative weights, a metric '
+             'left out has weight 0; METEOR is host-only and cannot be mixed), scored in one '
+             'launch on the GPU (ops/reward_mix.py).  --eval_metric then selects the model on '
+             'validation only.  Empty (default): the reward is the metric of --eval_metric')
     add('--val_scorer', type=str, default='strings', choices=['strings', 'tokens'],
         help='validation / test metrics: strings = decoded sentences through the Python '
              'scorers (reference route); tokens = token ids against the split\'s label table, '

@@ -245,18 +245,29 @@ class ConsensusScorer:
 def set_token_consensus(opt, dataset, device):
     """``--consensus_scorer tokens``: compute the training split's
     ``bcmrscores`` with :class:`ConsensusScorer` (``S = train_seq_per_img``,
-    leave-one-out, the metric of ``--eval_metric``) and set it on ``dataset``,
+    leave-one-out, the metric of ``--eval_metric``, or with ``--reward_mix`` the
+    same weighted sum of CIDEr-D / BLEU-4 / ROUGE-L as the reward) and set it on
+    ``dataset``,
     also in device tensors that are already cached.  Deterministic, so every
     data-parallel rank computes the same table itself.  Returns the matrix."""
     if getattr(opt, 'train_bcmrscores_pkl', None):
         raise ValueError('--consensus_scorer tokens computes the consensus scores itself; '
                          '--train_bcmrscores_pkl must not be given with it')
+    from .reward_mix import METRICS as MIX_METRICS, opt_weights
+    weights = opt_weights(opt)  # (--reward_mix: the baseline in the mixed metric)
     metric = consensus_metric(opt.eval_metric)
     key = (metric, int(opt.train_seq_per_img), int(opt.use_eos))
+    if weights is not None:
+        key = (weights, int(opt.train_seq_per_img), int(opt.use_eos))
     if getattr(dataset, '_token_consensus', None) == key:
         return dataset.bcmrscores
     scorer = ConsensusScorer(dataset, use_eos=opt.use_eos, device=device, backend='auto')
-    bcmr = scorer.scores(opt.train_seq_per_img, (metric,), remove_in_ref=True)[metric]
+    if weights is None:
+        bcmr = scorer.scores(opt.train_seq_per_img, (metric,), remove_in_ref=True)[metric]
+    else:  # (once at start-up, on the host: fp64 weighted sum of the metrics in use)
+        used = tuple(m for m, w in zip(MIX_METRICS, weights) if w)
+        per = scorer.scores(opt.train_seq_per_img, used, remove_in_ref=True)
+        bcmr = sum(w * per[m] for m, w in zip(MIX_METRICS, weights) if w)
     dataset.bcmrscores = bcmr
     dataset._token_consensus = key
     for d in dataset._device_cache.values():  # (normally empty: set before the first batch)

@@ -67,6 +67,10 @@ def build_scorer(opt, dataset, device):
     backend = 'auto'
     if getattr(opt, 'reward_device', 'gpu') == 'cpu':
         backend = 'cpu-ref'
+    if getattr(opt, 'reward_mix', ''):  # (--eval_metric then only selects the model)
+        from ..ops.reward_mix import MixedRewardScorer, opt_weights
+        return MixedRewardScorer(dataset, opt_weights(opt), use_eos=opt.use_eos, device=device,
+                                 backend=backend)
     if metric in ('CIDEr', 'MSRVTT', 'Loss'):
         return CiderDScorer(dataset, use_eos=opt.use_eos, device=device, backend=backend)
     if metric in ('Bleu_4', 'ROUGE_L'):
@@ -167,6 +171,9 @@ class Trainer:
         if engine is not None:
             engine.attach_optimizer(self)
         self.scorer = None
+        if getattr(opt, 'reward_mix', ''):
+            from ..ops.reward_mix import check_consensus_route
+            check_consensus_route(opt)
         # --consensus_scorer tokens: the training split's GT consensus scores
         # from its label table, before the first batch caches the dataset's
         # device tensors (ops/consensus.py; every rank computes the same table)
@@ -769,9 +776,10 @@ class Trainer:
         infos['TrainLoss'] = loss
         items = [('Epoch', infos['epoch']), ('Iter', infos['iter']), ('Loss', loss)]
         if self.rl_training:
+            name = 'mix' if getattr(opt, 'reward_mix', '') else opt.eval_metric
             items += [('Reward', vals[1]),
-                      ('{} (m)'.format(opt.eval_metric), vals[2]),
-                      ('{} (b)'.format(opt.eval_metric), vals[3])]
+                      ('{} (m)'.format(name), vals[2]),
+                      ('{} (b)'.format(name), vals[3])]
         if opt.use_ss == 1:
             items.append(('ss_prob', opt.ss_prob))
         if opt.use_mixer == 1:
