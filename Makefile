@@ -81,6 +81,9 @@ REWARD_MIX?=
 DECODE?=standard
 MBR_SAMPLES?=20
 MBR_TEMPERATURE?=1.0
+# the utility of consensus decoding in the grammar of REWARD_MIX, e.g.
+# MBR_MIX=CIDEr:1,Bleu_4:5,ROUGE_L:5 (empty: CIDEr-D); passed only when set
+MBR_MIX?=
 USE_MIXER?=0
 MIXER_FROM?=-1
 SS_K?=100
@@ -179,7 +182,7 @@ TRAIN_OPT=--beam_size $(BEAM_SIZE) --max_patience $(MAX_PATIENCE) --eval_metric 
 	--use_cst $(USE_CST) --scb_captions $(SCB_CAPTIONS) --scb_baseline $(SCB_BASELINE) \
 	--loglevel $(LOGLEVEL) --model_type $(MODEL_TYPE) --use_eos $(USE_EOS) \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
-	$(if $(REWARD_MIX),--reward_mix $(REWARD_MIX)) \
+	$(if $(REWARD_MIX),--reward_mix $(REWARD_MIX)) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX)) \
 	--model_file $@ --start_from $(START_FROM) --result_file $(basename $@)_test.json \
 	2>&1 | tee $(basename $@).log
 
@@ -192,7 +195,7 @@ endif
 TEST_OPT=--beam_size $(BEAM_SIZE) --language_eval $(VAL_LANG_EVAL) --test_seq_per_img $(TEST_SEQ_PER_IMG) \
 	--test_batch_size $(BATCH_SIZE) --loglevel $(LOGLEVEL) --result_file $@ \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
-	$(MBR_TEST_OPT)
+	$(MBR_TEST_OPT) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX))
 
 train: $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth
 $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth: \

@@ -169,6 +169,41 @@ static at::Tensor metric_score_cpu(const std::string& metric, at::Tensor hyps,
   return out;
 }
 
+// Peer mode of metric_score_cpu (metric mix, group = G >= 2): the native twin of
+// kernels/peer_mix.hip, [out (N), parts (N, 3)].  df: the df hash table
+// (ht_keys / ht_vals, CPU), None when CIDEr has weight 0.
+static std::vector<at::Tensor> peer_mix_score_cpu(
+    at::Tensor hyps, c10::optional<std::map<std::string, at::Tensor>> df, double log_ref_len,
+    int64_t use_eos, const std::vector<double>& weights, int64_t group) {
+  TORCH_CHECK(!hyps.is_cuda() && hyps.dim() == 2, "CPU hyps (N, T)");
+  TORCH_CHECK(group >= 2, "metric_score_cpu: group = ", group,
+              "; a peer pool has at least 2 rows (group = 0: reference tables)");
+  TORCH_CHECK(hyps.size(0) % group == 0, "metric_score_cpu: ", hyps.size(0),
+              " rows are not whole pools of ", group);
+  TORCH_CHECK(weights.size() == 3, "metric_score_cpu: weights = (CIDEr, Bleu_4, ROUGE_L)");
+  hyps = hyps.contiguous().to(at::kLong);
+  at::Tensor hk, hv;
+  if ((float)weights[0] != 0.f) {
+    TORCH_CHECK(df.has_value() && df->count("ht_keys") && df->count("ht_vals"),
+                "metric_score_cpu: CIDEr has a weight but no df tables (cider_tables: ht_keys "
+                "and ht_vals)");
+    hk = df->at("ht_keys").contiguous().to(at::kLong);
+    hv = df->at("ht_vals").contiguous().to(at::kFloat);
+    TORCH_CHECK(!hk.is_cuda() && !hv.is_cuda() && hk.numel() == hv.numel() && hk.numel() > 0 &&
+                    (hk.numel() & (hk.numel() - 1)) == 0,
+                "df hash table: CPU keys and values of one power-of-two size");
+  }
+  const int64_t N = hyps.size(0);
+  at::Tensor out = at::empty({N}, at::TensorOptions().dtype(at::kFloat));
+  at::Tensor parts = at::empty({N, 3}, at::TensorOptions().dtype(at::kFloat));
+  peer_mix_host(hyps.data_ptr<int64_t>(), (int)N, (int)hyps.size(1), (int)group,
+                hk.defined() ? hk.data_ptr<int64_t>() : nullptr,
+                hv.defined() ? hv.data_ptr<float>() : nullptr,
+                hk.defined() ? (uint32_t)hk.numel() : 0u, log_ref_len, (int)use_eos,
+                weights.data(), out.data_ptr<float>(), parts.data_ptr<float>());
+  return {out, parts};
+}
+
 // Validation scorer on the CPU: the host twins of kernels/corpus_metrics.hip.
 static at::Tensor bleu_stats_cpu(at::Tensor hyps, at::Tensor hyp_video,
                                  std::map<std::string, at::Tensor> t) {
@@ -252,7 +287,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
          c10::optional<std::map<std::string, at::Tensor>> tables, int64_t use_eos,
          c10::optional<at::Tensor> exclude,
          c10::optional<std::map<std::string, at::Tensor>> cider_tables, double log_ref_len,
-         c10::optional<std::vector<double>> weights) -> py::object {
+         c10::optional<std::vector<double>> weights, int64_t group) -> py::object {
+        if (group != 0) {
+          // peer mode (--mbr_mix; kernels/peer_mix.hip): hyps is B pools of G rows,
+          // every row scored against the others of its pool; cider_tables = the df
+          // hash table (ht_keys / ht_vals; None when w_c = 0), tables / hyp_video
+          // are not read
+          TORCH_CHECK(metric == "mix", "metric_score: peer mode (group > 0) is metric mix, got ",
+                      metric);
+          TORCH_CHECK(weights.has_value(), "metric_score: metric mix needs weights");
+          TORCH_CHECK(!(exclude.has_value() && exclude->defined()),
+                      "metric_score: peer mode (group > 0) takes no exclude");
+          return py::cast(cst::peer_mix_score(hyps, cider_tables, log_ref_len, use_eos, *weights,
+                                              group));
+        }
         if (metric == "mix") {
           TORCH_CHECK(weights.has_value(), "metric_score: metric mix needs weights");
           TORCH_CHECK(!(exclude.has_value() && exclude->defined()),
@@ -267,12 +315,37 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       },
       py::arg("metric"), py::arg("hyps"), py::arg("hyp_video"), py::arg("tables"),
       py::arg("use_eos"), py::arg("exclude") = py::none(), py::arg("cider_tables") = py::none(),
-      py::arg("log_ref_len") = 0.0, py::arg("weights") = py::none(),
+      py::arg("log_ref_len") = 0.0, py::arg("weights") = py::none(), py::arg("group") = 0,
       "Bleu_4 | ROUGE_L sentence scores on the GPU, or their weighted mix with CIDEr-D "
-      "(metric mix); one launch, capturable");
-  m.def("metric_score_cpu", &cst::metric_score_cpu, py::arg("metric"), py::arg("hyps"),
-        py::arg("hyp_video"), py::arg("tables"), py::arg("use_eos"),
-        py::arg("exclude") = py::none());
+      "(metric mix; group = G >= 2: every row against the others of its pool of G); one "
+      "launch, capturable");
+  // group = G >= 2 with metric mix: the native twin of the peer mode above,
+  // [out (N), parts (N, 3)], any G; group = 0: the sentence scorers, as before
+  m.def(
+      "metric_score_cpu",
+      [](const std::string& metric, at::Tensor hyps, at::Tensor hyp_video,
+         c10::optional<std::map<std::string, at::Tensor>> tables, int64_t use_eos,
+         c10::optional<at::Tensor> exclude,
+         c10::optional<std::map<std::string, at::Tensor>> cider_tables, double log_ref_len,
+         c10::optional<std::vector<double>> weights, int64_t group) -> py::object {
+        if (group != 0) {
+          TORCH_CHECK(metric == "mix",
+                      "metric_score_cpu: peer mode (group > 0) is metric mix, got ", metric);
+          TORCH_CHECK(weights.has_value(), "metric_score_cpu: metric mix needs weights");
+          TORCH_CHECK(!(exclude.has_value() && exclude->defined()),
+                      "metric_score_cpu: peer mode (group > 0) takes no exclude");
+          return py::cast(cst::peer_mix_score_cpu(hyps, cider_tables, log_ref_len, use_eos,
+                                                  *weights, group));
+        }
+        TORCH_CHECK(!weights.has_value() && !cider_tables.has_value(),
+                    "metric_score_cpu: weights / cider_tables go with peer mode (metric mix, "
+                    "group > 0) only");
+        TORCH_CHECK(tables.has_value(), "metric_score_cpu: tables must be given");
+        return py::cast(cst::metric_score_cpu(metric, hyps, hyp_video, *tables, use_eos, exclude));
+      },
+      py::arg("metric"), py::arg("hyps"), py::arg("hyp_video"), py::arg("tables"),
+      py::arg("use_eos"), py::arg("exclude") = py::none(), py::arg("cider_tables") = py::none(),
+      py::arg("log_ref_len") = 0.0, py::arg("weights") = py::none(), py::arg("group") = 0);
   m.def("flat_adam_step", &cst::flat_adam_step);
   m.def("refresh_shadows", &cst::refresh_shadows);
   m.def("vocab_fwd_bench", &cst::vocab_fwd_bench);

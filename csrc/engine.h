@@ -104,6 +104,10 @@ std::vector<at::Tensor> reward_mix_score(
     c10::optional<std::map<std::string, at::Tensor>> cider_tables,
     c10::optional<std::map<std::string, at::Tensor>> sent_tables, double log_ref_len,
     int64_t use_eos, std::vector<double> weights);
+std::vector<at::Tensor> peer_mix_score(at::Tensor hyps,
+                                       c10::optional<std::map<std::string, at::Tensor>> df,
+                                       double log_ref_len, int64_t use_eos,
+                                       std::vector<double> weights, int64_t group);
 at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v,
                           at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
                           double b1, double b2, double eps, double clip, double gscale,

@@ -75,6 +75,21 @@ void rouge_l_score_host(const int64_t* hyps, int N, int T, const int64_t* hyp_vi
                         const MetricTablesView& t, int use_eos, float* out,
                         const int64_t* exclude = nullptr);
 
+// Peer scoring under a mixed utility (peer_mix_host.cpp; consensus / MBR decoding,
+// the twin of csrc/kernels/peer_mix.hip): hyps (N, T) in pools of G consecutive rows, the
+// references of row i are the G - 1 other rows of its pool.  parts (N, 3) = peer
+// CIDEr-D (cider_peers_host), sentence BLEU-4 and ROUGE-L against those
+// references -- i.e. build_metric_tables on the pool rows + the scorers above with
+// exclude[i] = i mod G; out (N) = ((w[0] * c) + (w[1] * b)) + (w[2] * r) in fp32.
+// A metric of weight 0 is not computed and its column is exactly 0; the df hash
+// table is read only when w[0] != 0 and may be null otherwise.  Any G >= 2 with
+// N % G == 0, T <= METRIC_MAXT, finite non-negative weights that are not all
+// zero (std::invalid_argument otherwise; CIDEr-D and BLEU also reject tokens
+// above METRIC_MAX_TOKEN).
+void peer_mix_host(const int64_t* hyps, int N, int T, int G, const int64_t* ht_keys,
+                   const float* ht_vals, uint32_t ht_cap, double log_ref_len, int use_eos,
+                   const double w[3], float* out, float* parts);
+
 // Validation scorer (ops/corpus_metrics.py), fp64 host twins of
 // csrc/kernels/corpus_metrics.hip.  Hypotheses are reduced without EOS.
 //  * bleu_stats_host: per hypothesis correct[4], guess[4], tlen, rlen (10 ints),

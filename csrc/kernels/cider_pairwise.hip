@@ -38,39 +38,17 @@
 
 #include "../common.h"
 #include "../cider_common.h"
+#include "peer_common.h"
 
 namespace cst {
 
-constexpr int PEER_MAXT = 63;          // compact_hypothesis: one wave, W <= 63 (+ EOS)
-constexpr int PEER_MAXG = 64;
-constexpr int PEER_MAX_SLOTS = 2048;   // G * (T + 1): 64 x 32 or 32 x 64
-constexpr int PEER_HDR_BYTES = 32;
 constexpr int PEER_MAX_LDS = 48 * PEER_MAX_SLOTS + PEER_HDR_BYTES * PEER_MAXG;  // 100,352 B
-constexpr int PEER_WAVES = 16;
 
 static inline int peer_row_bytes(int T) { return 48 * (T + 1) + PEER_HDR_BYTES; }
 
 bool peer_cider_supported(int64_t G, int64_t T) {
   return G >= 2 && G <= PEER_MAXG && T >= 1 && T <= PEER_MAXT && G * (T + 1) <= PEER_MAX_SLOTS;
 }
-
-// The n-grams of a row of W tokens as one list: order n + 1 has max(W - n, 0)
-// entries and starts at o[n]; o[4] is the total.
-struct PeerSpan {
-  int o1, o2, o3, E;
-  __device__ __forceinline__ explicit PeerSpan(int W) {
-    o1 = W;
-    o2 = o1 + max(W - 1, 0);
-    o3 = o2 + max(W - 2, 0);
-    E = o3 + max(W - 3, 0);
-  }
-  // entry x -> order index n (0..3) and position in the order
-  __device__ __forceinline__ int order(int x, int& pos) const {
-    const int n = (x >= o1) + (x >= o2) + (x >= o3);
-    pos = x - (n == 0 ? 0 : n == 1 ? o1 : n == 2 ? o2 : o3);
-    return n;
-  }
-};
 
 __global__ __launch_bounds__(PEER_WAVES * 64) void cider_pairwise_kernel(
     const int64_t* __restrict__ hyps, int T, int G, const int64_t* __restrict__ ht_keys,

@@ -172,6 +172,22 @@ struct BleuTables {
   const int32_t* ng_arg;   // (leave-one-out only)
 };
 
+// The closing formula of sentence BLEU-4 (eval/metrics.py::Bleu) in fp64, rounded
+// once: the clipped matches per order, the hypothesis length and the closest
+// reference length.  One copy for the table kernels and peer_mix_kernel, so equal
+// integers give equal bits.
+__device__ __forceinline__ float bleu4_close(const int* correct, int W, int rlen) {
+  const double tiny = 1e-15, small = 1e-9;
+  double b = 1.0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    b *= ((double)correct[k] + tiny) / ((double)max(0, W - k) + small);
+  double s = pow(b, 0.25);
+  const double ratio = ((double)W + tiny) / ((double)rlen + small);
+  if (ratio < 1.0) s *= exp(1.0 - 1.0 / ratio);
+  return (float)s;
+}
+
 // Steps 3-5 of bleu4_kernel by one whole wave, from the hypothesis' checked keys
 // and first-occurrence term frequencies in LDS.  The score, valid in lane 0.
 __device__ __forceinline__ float bleu4_refs(const BleuTables& t, const uint64_t (*s_key)[RW_MAXT],
@@ -211,18 +227,7 @@ __device__ __forceinline__ float bleu4_refs(const BleuTables& t, const uint64_t 
   }
   best = wave_min_i(best);
   float res = 0.f;
-  if (lane == 0 && r1 > r0) {
-    const double tiny = 1e-15, small = 1e-9;
-    const int rlen = best & 0xff;
-    double b = 1.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-      b *= ((double)correct[k] + tiny) / ((double)max(0, W - k) + small);
-    double s = pow(b, 0.25);
-    const double ratio = ((double)W + tiny) / ((double)rlen + small);
-    if (ratio < 1.0) s *= exp(1.0 - 1.0 / ratio);
-    res = (float)s;
-  }
+  if (lane == 0 && r1 > r0) res = bleu4_close(correct, W, best & 0xff);
   return res;
 }
 
@@ -233,6 +238,35 @@ struct RougeTables {
   const int32_t* ref_tok_off;
   const int32_t* ref_tok;
 };
+
+// One reference of `n` tokens (lane a < n holds token a in rtok, other lanes a
+// value no hypothesis token has) against the hypothesis (htok = token `lane`,
+// -1 past its end): the LCS length by the bit-parallel recurrence on one 64-bit
+// word, wave-uniform.
+__device__ __forceinline__ int lcs_bits(int htok, int rtok, int n) {
+  uint64_t V = ~0ull;
+  for (int a = 0; a < n; ++a) {
+    const int c = __builtin_amdgcn_readlane(rtok, a);
+    const uint64_t M = __ballot(htok == c);
+    const uint64_t U = V & M;
+    V = (V + U) | (V - U);
+  }
+  return __popcll(~V);
+}
+
+// The closing formula of ROUGE-L (eval/metrics.py::Rouge, beta 1.2) in fp64,
+// rounded once: best_l / W the largest LCS precision, rec_l / rec_n the largest
+// LCS recall.  One copy for the table kernels and peer_mix_kernel.
+__device__ __forceinline__ float rouge_l_close(int best_l, int W, int rec_l, int rec_n) {
+  float res = 0.f;
+  if (W > 0 && best_l > 0 && rec_l > 0) {
+    const double beta = 1.2, b2 = beta * beta;
+    const double p = (double)best_l / (double)W;
+    const double rc = (double)rec_l / (double)rec_n;
+    res = (float)(((1.0 + b2) * p * rc) / (rc + b2 * p));
+  }
+  return res;
+}
 
 // rouge_l_kernel after the compaction, by one whole wave: htok = hypothesis
 // token `lane` (-1 past the end).  The score, valid in lane 0.
@@ -266,24 +300,12 @@ __device__ __forceinline__ float rouge_l_refs(const RougeTables& t, int htok, in
       nxt = lane < min(o1 - o0, 64) ? t.ref_tok[o0 + lane] : -2;
     }
     r = rn;
-    uint64_t V = ~0ull;
-    for (int a = 0; a < n; ++a) {
-      const int c = __builtin_amdgcn_readlane(rtok, a);
-      const uint64_t M = __ballot(htok == c);
-      const uint64_t U = V & M;
-      V = (V + U) | (V - U);
-    }
-    const int l = __popcll(~V);
+    const int l = lcs_bits(htok, rtok, n);
     best_l = max(best_l, l);
     if (n > 0 && l * rec_n > rec_l * n) rec_l = l, rec_n = n;
   }
   float res = 0.f;
-  if (lane == 0 && W > 0 && best_l > 0 && rec_l > 0) {
-    const double beta = 1.2, b2 = beta * beta;
-    const double p = (double)best_l / (double)W;
-    const double rc = (double)rec_l / (double)rec_n;
-    res = (float)(((1.0 + b2) * p * rc) / (rc + b2 * p));
-  }
+  if (lane == 0) res = rouge_l_close(best_l, W, rec_l, rec_n);
   return res;
 }
 

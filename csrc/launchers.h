@@ -120,6 +120,17 @@ void launch_reward_mix(const int64_t* hyps, int T, const int64_t* hyp_video, int
                        const MixCiderArgs& c, const MixSentArgs& s, int use_eos, float w_c,
                        float w_b, float w_r, float* out, float* parts, hipStream_t stream);
 
+// peer_mix.hip: peer w_c * CIDEr-D + w_b * BLEU-4 + w_r * ROUGE-L (consensus / MBR
+// decoding under a mixed utility).  hyps (B * G, T): every row against the G - 1
+// other rows of its pool of G as references; out (B * G), parts (B * G, 3) = the
+// three scores (0 where the weight is 0).  The df hash table is read only when
+// w_c > 0 and may be null otherwise.  Pools within peer_cider_supported(G, T);
+// the launcher throws outside it.
+void launch_peer_mix(const int64_t* hyps, int T, int G, int B, const int64_t* ht_keys,
+                     const float* ht_vals, uint32_t ht_cap, float log_ref_len, int use_eos,
+                     float w_c, float w_b, float w_r, float* out, float* parts,
+                     hipStream_t stream);
+
 // corpus_metrics.hip: per-hypothesis statistics of corpus BLEU (10 x int32) and
 // METEOR (6 x int32 + the fp64 segment score), one wavefront each (T <= 64)
 void launch_bleu_stats(const int64_t* hyps, int T, const int64_t* hyp_video, int N, int Nv,

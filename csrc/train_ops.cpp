@@ -445,6 +445,58 @@ std::vector<at::Tensor> reward_mix_score(
   return {out, parts};
 }
 
+// Peer scores under a mixed utility (kernels/peer_mix.hip; consensus / MBR
+// decoding): rows [k * group, (k + 1) * group) of hyps are one pool, every row is
+// scored against the others of its pool.  weights = (w_c, w_b, w_r) over CIDEr-D,
+// BLEU-4, ROUGE-L; returns {out (N), parts (N, 3)}.  Only the df hash table
+// (ht_keys / ht_vals of `df`) is read, and only when w_c > 0: it may be None
+// otherwise.  One launch, no allocation besides the results and no
+// synchronisation: capturable.  Everything is checked here, before the launch.
+std::vector<at::Tensor> peer_mix_score(at::Tensor hyps,
+                                       c10::optional<std::map<std::string, at::Tensor>> df,
+                                       double log_ref_len, int64_t use_eos,
+                                       std::vector<double> weights, int64_t group) {
+  check_cuda(hyps, "hyps");
+  TORCH_CHECK(hyps.scalar_type() == at::kLong && hyps.dim() == 2 && hyps.is_contiguous(),
+              "hyps: contiguous int64 (N, T)");
+  const int64_t N = hyps.size(0), T = hyps.size(1);
+  TORCH_CHECK(group >= 2, "metric_score: group = ", group,
+              "; a peer pool has at least 2 rows (group = 0: reference tables)");
+  TORCH_CHECK(N % group == 0, "metric_score: ", N, " rows are not whole pools of ", group);
+  TORCH_CHECK(peer_cider_supported(group, T), "metric_score: a pool of group = ", group,
+              " rows of T = ", T, " tokens is outside the peer kernel's limit: group <= 64, "
+              "1 <= T <= 63 and group * (T + 1) <= 2048 (64 rows of 31 tokens, 32 rows of 63)");
+  TORCH_CHECK(weights.size() == 3, "metric_score: weights = (CIDEr, Bleu_4, ROUGE_L)");
+  for (double w : weights)
+    TORCH_CHECK(std::isfinite(w) && w >= 0.0, "metric_score: weight ", w,
+                " is negative or not finite");
+  const float w_c = (float)weights[0], w_b = (float)weights[1], w_r = (float)weights[2];
+  TORCH_CHECK(w_c != 0.f || w_b != 0.f || w_r != 0.f, "metric_score: all weights are zero");
+  const int64_t* hk = nullptr;
+  const float* hv = nullptr;
+  uint32_t cap = 0;
+  if (w_c != 0.f) {
+    TORCH_CHECK(df.has_value() && df->count("ht_keys") && df->count("ht_vals"),
+                "metric_score: CIDEr has a weight but no df tables (cider_tables: ht_keys and "
+                "ht_vals)");
+    const at::Tensor& k = df->at("ht_keys");
+    const at::Tensor& v = df->at("ht_vals");
+    check_cuda(k, "ht_keys");
+    check_cuda(v, "ht_vals");
+    TORCH_CHECK(k.scalar_type() == at::kLong && v.scalar_type() == at::kFloat &&
+                    k.is_contiguous() && v.is_contiguous() && k.numel() == v.numel() &&
+                    k.numel() > 0 && (k.numel() & (k.numel() - 1)) == 0,
+                "df hash table: int64 keys and fp32 values of one power-of-two size");
+    hk = k.data_ptr<int64_t>(), hv = v.data_ptr<float>(), cap = (uint32_t)k.numel();
+  }
+  at::Tensor out = at::empty({N}, hyps.options().dtype(at::kFloat));
+  at::Tensor parts = at::empty({N, 3}, hyps.options().dtype(at::kFloat));
+  launch_peer_mix(hyps.data_ptr<int64_t>(), (int)T, (int)group, (int)(N / group), hk, hv, cap,
+                  (float)log_ref_len, (int)use_eos, w_c, w_b, w_r, out.data_ptr<float>(),
+                  parts.data_ptr<float>(), cur_stream());
+  return {out, parts};
+}
+
 // Validation scorer (kernels/corpus_metrics.hip): per-hypothesis statistics of
 // corpus BLEU ((N, 10) int32) or METEOR ((N, 6) int32 and the (N) fp64 segment
 // scores) against the tables of metric_build_tables (METEOR: built with stem

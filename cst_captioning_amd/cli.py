@@ -135,11 +135,22 @@ def train_main(argv=None):
     return infos
 
 
+def _mbr_needs_df(opt):
+    """--decode mbr: whether the utility has a CIDEr-D term (--mbr_mix empty: CIDEr-D)."""
+    mix = getattr(opt, 'mbr_mix', '') or ''
+    if not mix:
+        return True
+    from .ops.reward_mix import parse_reward_mix
+    return parse_reward_mix(mix, '--mbr_mix')[0] != 0
+
+
 def test_main(argv=None):
     opt = parse_opts(argv)
     ctx = init_distributed()
     setup_logging(opt, ctx.rank)
-    if opt.decode == 'mbr' and not opt.synthetic:
+    # --mbr_mix without CIDEr reads no df table: none is asked for
+    mbr_df = opt.decode == 'mbr' and _mbr_needs_df(opt)
+    if mbr_df and not opt.synthetic:
         # consensus decoding scores under the TRAINING set's df table (the
         # synthetic split carries its own); refused here, before the model is built
         if not isinstance(opt.train_cached_tokens, str):
@@ -161,7 +172,7 @@ def test_main(argv=None):
     loader = CaptionLoader(te, opt.test_batch_size, opt.test_seq_per_img, 'test', ctx.device)
     from .train.trainer import Trainer, check_val_scorer
     check_val_scorer(opt, loader)
-    if opt.decode == 'mbr' and opt.synthetic and te.df is None:
+    if mbr_df and opt.synthetic and te.df is None:
         raise ValueError('--decode mbr needs a CIDEr-D document-frequency table; the '
                          'synthetic split has none')
     assert opt.vocab_size == loader.get_vocab_size()

@@ -27,6 +27,18 @@ def reward_mix_arg(spec):
     return spec
 
 
+def mbr_mix_arg(spec):
+    """``--mbr_mix``: '' (CIDEr-D) or a specification of the ``--reward_mix`` grammar."""
+    if spec == '':
+        return spec
+    from .ops.reward_mix import parse_reward_mix
+    try:
+        parse_reward_mix(spec, '--mbr_mix')
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return spec
+
+
 def build_parser():
     p = argparse.ArgumentParser(
         description='MI355X-native consensus/self-critical video captioning trainer')
@@ -135,6 +147,12 @@ def build_parser():
         help='--decode mbr: multinomial samples per video beside the standard caption')
     add('--mbr_temperature', type=float, default=1.0,
         help='--decode mbr: sampling temperature of those samples')
+    add('--mbr_mix', type=mbr_mix_arg, default='', metavar='METRIC:WEIGHT[,...]',
+        help='--decode mbr: the utility the captions of a pool are scored under, in the grammar '
+             'of --reward_mix, e.g. CIDEr:1,Bleu_4:5,ROUGE_L:5 (peer CIDEr-D on its x10 scale, '
+             'sentence Bleu_4 and ROUGE_L with the other captions of the pool as references), '
+             'one launch on the GPU (ops/mbr.py PeerMix).  The document-frequency table is '
+             'needed only when CIDEr has a weight.  Empty (default): CIDEr-D')
     add('--consensus_scorer', type=str, default='file', choices=['file', 'tokens'],
         help='GT consensus scores of CST / WXE training: file = read --train_bcmrscores_pkl '
              '(prepro/evalscores.py); tokens = computed at start-up (when --use_cst 1) from the training label '

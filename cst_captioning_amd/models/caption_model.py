@@ -227,7 +227,8 @@ class CaptionModel(nn.Module):
         (``N = opt['mbr_samples']``, ``opt['mbr_temperature']``, one expanded
         call), all padded with 0 to one width; ``G = N + 1``.  Every row is
         scored against its peers by ``opt['mbr_scorer']``
-        (:class:`..ops.mbr.PeerCiderD`) and the best row is returned, index 0
+        (:class:`..ops.mbr.PeerCiderD`, or :class:`..ops.mbr.PeerMix` for a
+        mixed utility) and the best row is returned, index 0
         winning ties.  Returns ``(seq (B, T), logprobs (B, T), info)`` with
         ``info = {'pool': (B, G, T), 'scores': (B, G), 'best': (B,)}``.  The
         sampling seeds come from torch's generator.  Pooling, scoring and

@@ -24,6 +24,11 @@ test split never reads that split's labels.
 the CIDEr-D similarity with ``i`` as the hypothesis and ``j`` as the reference.
 Identical rows of a pool are ordinary peers: a caption drawn three times gets
 three votes.
+
+:class:`PeerMix` (``--mbr_mix``) scores the same pools under a weighted sum of
+peer CIDEr-D, sentence BLEU-4 and ROUGE-L, so a model trained with
+``--reward_mix`` is decoded under the utility it was trained on
+(``csrc/kernels/peer_mix.hip``, one launch).
 """
 import math
 
@@ -133,6 +138,128 @@ class PeerCiderD:
         among the rows that equal the pool's maximum score (index 0, the
         standard decode, wins ties).  Stays on ``hyps.device``, no host
         synchronisation."""
+        scores = self.score(hyps, group).view(-1, int(group))
+        return select_best(scores), scores
+
+
+class PeerMix:
+    """Peer scores under a mixed utility (``--mbr_mix``): ``w_c * CIDErD + w_b *
+    BLEU4 + w_r * ROUGE_L`` of every row against the other rows of its pool.
+
+    ``parts[i] = (peer CIDEr-D as PeerCiderD, sentence BLEU-4, ROUGE-L of
+    eval/metrics.py with the G - 1 other rows as references)``; a metric of
+    weight 0 is not computed and its column is exactly 0.  ``df`` is the
+    ``(keys, vals, ref_len)`` triple of :class:`PeerCiderD`; it is read only when
+    ``w_c > 0`` and may be None otherwise.  ``vocab_size``: the model's, when
+    known.  The interface is :class:`PeerCiderD`'s (``score`` is the
+    blend), so ``CaptionModel.sample_mbr`` takes either.
+
+      * ``backend='gpu'``: ``csrc/kernels/peer_mix.hip``, one launch
+        (``metric_score('mix', ..., group=G)``), the limits of the CIDEr-D kernel;
+      * ``backend='cpu'``: the native twin (``metric_score_cpu('mix', ...,
+        group=G)``), any ``G >= 2``;
+      * ``backend='cpu-ref'``: ``CiderD.score_one`` and the ``Bleu`` / ``Rouge``
+        classes on index strings.
+
+    The native backends pack n-grams at 16 bits per token: a vocabulary with ids
+    over 65,534 is refused here.
+    """
+
+    def __init__(self, df, weights, use_eos=0, device='cpu', backend='auto', vocab_size=None):
+        from .reward_mix import MAX_TOKEN
+        weights = tuple(float(x) for x in weights)
+        if len(weights) != 3:
+            raise ValueError('weights: (CIDEr, Bleu_4, ROUGE_L), got %r' % (weights,))
+        if any(not math.isfinite(x) or x < 0 for x in weights) or not any(weights):
+            raise ValueError('weights must be finite, non-negative and not all zero, got %r'
+                             % (weights,))
+        if weights[0] and df is None:
+            raise ValueError('peer CIDEr-D has weight %g and needs a CIDEr-D document-frequency '
+                             'table' % weights[0])
+        if not weights[0]:
+            df = None  # (never read)
+        self.weights = weights
+        self.use_eos = int(use_eos)
+        self.device = torch.device(device)
+        if backend == 'auto':
+            backend = 'gpu' if (self.device.type == 'cuda' and _ext.available()) else 'cpu-ref'
+            if backend == 'cpu-ref' and _ext.host_available():
+                backend = 'cpu'
+        if backend not in ('gpu', 'cpu', 'cpu-ref'):
+            raise ValueError('unknown backend %r' % (backend,))
+        if backend == 'gpu' and self.device.type != 'cuda':
+            raise ValueError("backend 'gpu' needs a cuda device, got %s" % (self.device,))
+        if backend != 'cpu-ref' and vocab_size is not None and vocab_size - 1 > MAX_TOKEN:
+            raise ValueError('vocabulary of %d entries: token ids over 65,534 do not fit the '
+                             'packed n-gram keys' % vocab_size)
+        self.backend = backend
+        # CIDEr-D: the oracle and the df hash table are PeerCiderD's
+        self.cider = None if df is None else PeerCiderD(df, use_eos, device, backend)
+        self.log_ref_len = 0.0 if self.cider is None else self.cider.log_ref_len
+        self._tables = None if self.cider is None else self.cider._tables
+
+    _check = staticmethod(PeerCiderD._check)
+
+    def parts_reference(self, hyps, group):
+        """(N, 3) fp64 scores of the Python oracles (0 where the weight is 0)."""
+        from ..eval.metrics import Bleu, Rouge
+        group = self._check(hyps, group)
+        w_c, w_b, w_r = self.weights
+        h = hyps.detach().cpu().numpy()
+        parts = np.zeros((len(h), 3), dtype=np.float64)
+        if w_c:
+            parts[:, 0] = self.cider.score_reference(hyps, group)
+        if w_b or w_r:
+            strs = [array_to_str(r, self.use_eos) for r in h]
+            res = {i: [s] for i, s in enumerate(strs)}
+            gts = {}
+            for p0 in range(0, len(strs), group):
+                pool = strs[p0:p0 + group]
+                for i in range(group):
+                    gts[p0 + i] = pool[:i] + pool[i + 1:]
+            if w_b and len(strs):
+                parts[:, 1] = np.asarray(Bleu(4).compute_score(gts, res)[1][-1])
+            if w_r and len(strs):
+                parts[:, 2] = np.asarray(Rouge().compute_score(gts, res)[1])
+        return parts
+
+    def score_reference(self, hyps, group):
+        """fp64 blend of the Python oracles: ``(N,)`` float64 numpy."""
+        return self.parts_reference(hyps, group) @ np.asarray(self.weights, dtype=np.float64)
+
+    def score_both(self, hyps, group):
+        """``(out (N,), parts (N, 3))`` float32 on ``hyps.device``.  The GPU
+        backend launches one kernel and does not synchronise."""
+        group = self._check(hyps, group)
+        if self.backend == 'gpu':
+            h = hyps.contiguous()
+            out, parts = _ext.ops().metric_score(
+                'mix', h, h.new_zeros(0), None, self.use_eos, cider_tables=self._tables,
+                log_ref_len=self.log_ref_len, weights=list(self.weights), group=group)
+            return out, parts
+        if self.backend == 'cpu':
+            h = hyps.detach().cpu().contiguous()
+            out, parts = _ext.ops().metric_score_cpu(
+                'mix', h, h.new_zeros(0), None, self.use_eos, cider_tables=self._tables,
+                log_ref_len=self.log_ref_len, weights=list(self.weights), group=group)
+            return out.to(hyps.device), parts.to(hyps.device)
+        parts = self.parts_reference(hyps, group).astype(np.float32)
+        w = np.asarray(self.weights, dtype=np.float32)
+        out = (w[0] * parts[:, 0] + w[1] * parts[:, 1]) + w[2] * parts[:, 2]  # (fp32, as the kernel)
+        return (torch.from_numpy(out.astype(np.float32)).to(hyps.device),
+                torch.from_numpy(parts).to(hyps.device))
+
+    def score_parts(self, hyps, group):
+        """(N, 3) float32: peer CIDEr-D, BLEU-4, ROUGE-L of every row."""
+        return self.score_both(hyps, group)[1]
+
+    def score(self, hyps, group):
+        """(N,) float32 blended peer scores on ``hyps.device``."""
+        return self.score_both(hyps, group)[0]
+
+    def select(self, hyps, group):
+        """``(best (B,), scores (B, G))`` under the blend, the tie rule of
+        :func:`select_best`; stays on ``hyps.device``."""
         scores = self.score(hyps, group).view(-1, int(group))
         return select_best(scores), scores
 

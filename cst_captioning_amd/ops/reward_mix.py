@@ -37,39 +37,42 @@ METRICS = ('CIDEr', 'Bleu_4', 'ROUGE_L')
 MAX_TOKEN = 65534
 
 
-def parse_reward_mix(spec):
+def parse_reward_mix(spec, flag='--reward_mix'):
     """``'CIDEr:1,Bleu_4:5'`` -> ``(w_c, w_b, w_r)`` floats in the order of
     :data:`METRICS`; a metric left out has weight 0.  ``ValueError`` naming the
     problem for an unknown metric, METEOR, a metric given twice, a malformed,
-    negative or non-finite weight, and all weights zero."""
+    negative or non-finite weight, and all weights zero.  ``flag``: the
+    command-line flag the messages name (``--mbr_mix`` takes the same grammar)."""
+    def bad(msg):
+        return ValueError('%s: %s' % (flag, msg))
+
     if not isinstance(spec, str) or not spec.strip():
-        raise ValueError('--reward_mix: empty specification')
+        raise bad('empty specification')
     w = {}
     for item in spec.split(','):
         name, sep, val = item.strip().partition(':')
         name, val = name.strip(), val.strip()
         if not sep or not name or not val:
-            raise ValueError('--reward_mix: %r is not METRIC:WEIGHT' % (item.strip(),))
+            raise bad('%r is not METRIC:WEIGHT' % (item.strip(),))
         if name == 'METEOR':
-            raise ValueError('--reward_mix: METEOR is scored on the host only and cannot be '
-                             'mixed (use --eval_metric METEOR for a METEOR reward)')
+            raise bad('METEOR is scored on the host only and cannot be '
+                      'mixed (use --eval_metric METEOR for a METEOR reward)')
         if name not in METRICS:
-            raise ValueError('--reward_mix: unknown metric %r (one of %s)'
-                             % (name, ', '.join(METRICS)))
+            raise bad('unknown metric %r (one of %s)' % (name, ', '.join(METRICS)))
         if name in w:
-            raise ValueError('--reward_mix: metric %s appears twice' % name)
+            raise bad('metric %s appears twice' % name)
         try:
             x = float(val)
         except ValueError:
-            raise ValueError('--reward_mix: weight %r of %s is not a number' % (val, name))
+            raise bad('weight %r of %s is not a number' % (val, name))
         if not math.isfinite(x):
-            raise ValueError('--reward_mix: weight %r of %s is not finite' % (val, name))
+            raise bad('weight %r of %s is not finite' % (val, name))
         if x < 0:
-            raise ValueError('--reward_mix: weight %r of %s is negative' % (val, name))
+            raise bad('weight %r of %s is negative' % (val, name))
         w[name] = x
     weights = tuple(w.get(m, 0.0) for m in METRICS)
     if not any(weights):
-        raise ValueError('--reward_mix: all weights are zero')
+        raise bad('all weights are zero')
     return weights
 
 

@@ -816,10 +816,16 @@ class Trainer:
         opt = self.opt
         if getattr(opt, 'decode', 'standard') != 'mbr':
             return None
+        # --mbr_mix: the utility's weights; the df table only when CIDEr has one
+        mix = getattr(opt, 'mbr_mix', '') or ''
+        weights = None
+        if mix:
+            from ..ops.reward_mix import parse_reward_mix
+            weights = parse_reward_mix(mix, '--mbr_mix')
         df = getattr(opt, 'mbr_df', None)
         if df is None and self.train_loader is not None:
             df = self.train_loader.ds.df
-        if df is None:
+        if df is None and (weights is None or weights[0]):
             raise ValueError('--decode mbr scores captions under CIDEr-D and needs a '
                              'document-frequency table: the training dataset has none '
                              '(--train_cached_tokens)')
@@ -827,7 +833,11 @@ class Trainer:
             raise ValueError('--mbr_samples must be at least 1, got %d' % opt.mbr_samples)
         if not float(opt.mbr_temperature) > 0:
             raise ValueError('--mbr_temperature must be positive, got %r' % opt.mbr_temperature)
-        from ..ops.mbr import PeerCiderD
+        from ..ops.mbr import PeerCiderD, PeerMix
+        if weights is not None:
+            return PeerMix(df if weights[0] else None, weights, use_eos=opt.use_eos,
+                           device=self.device, backend='auto',
+                           vocab_size=getattr(opt, 'vocab_size', None))
         return PeerCiderD(df, use_eos=opt.use_eos, device=self.device, backend='auto')
 
     def decode_opts(self):
