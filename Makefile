@@ -84,6 +84,9 @@ MBR_TEMPERATURE?=1.0
 # the utility of consensus decoding in the grammar of REWARD_MIX, e.g.
 # MBR_MIX=CIDEr:1,Bleu_4:5,ROUGE_L:5 (empty: CIDEr-D); passed only when set
 MBR_MIX?=
+# EMA of the parameters kept by the fused Adam pass; validation, the best score
+# and the best checkpoint then use the averaged weights (0 = off)
+EMA_DECAY?=0
 USE_MIXER?=0
 MIXER_FROM?=-1
 SS_K?=100
@@ -183,6 +186,7 @@ TRAIN_OPT=--beam_size $(BEAM_SIZE) --max_patience $(MAX_PATIENCE) --eval_metric 
 	--loglevel $(LOGLEVEL) --model_type $(MODEL_TYPE) --use_eos $(USE_EOS) \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
 	$(if $(REWARD_MIX),--reward_mix $(REWARD_MIX)) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX)) \
+	--ema_decay $(EMA_DECAY) \
 	--model_file $@ --start_from $(START_FROM) --result_file $(basename $@)_test.json \
 	2>&1 | tee $(basename $@).log
 

@@ -346,8 +346,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
       py::arg("metric"), py::arg("hyps"), py::arg("hyp_video"), py::arg("tables"),
       py::arg("use_eos"), py::arg("exclude") = py::none(), py::arg("cider_tables") = py::none(),
       py::arg("log_ref_len") = 0.0, py::arg("weights") = py::none(), py::arg("group") = 0);
-  m.def("flat_adam_step", &cst::flat_adam_step);
-  m.def("refresh_shadows", &cst::refresh_shadows);
+  // ema (none or empty: off) / ema_decay: the parameter EMA kept by the update pass
+  m.def("flat_adam_step", &cst::flat_adam_step, py::arg("p"), py::arg("g"), py::arg("m"),
+        py::arg("v"), py::arg("partials"), py::arg("scal"), py::arg("skip"), py::arg("hyper"),
+        py::arg("b1"), py::arg("b2"), py::arg("eps"), py::arg("clip"), py::arg("gscale"),
+        py::arg("phase"), py::arg("shadow_meta"), py::arg("shadow_dst"),
+        py::arg("ema") = py::none(), py::arg("ema_decay") = 0.0);
+  // swap_with: p and swap_with are exchanged, the shadows written from the new p
+  m.def("refresh_shadows", &cst::refresh_shadows, py::arg("p"), py::arg("shadow_meta"),
+        py::arg("shadow_dst"), py::arg("swap_with") = py::none());
   m.def("vocab_fwd_bench", &cst::vocab_fwd_bench);
   m.def("vgrad_colsum_bench", &cst::vgrad_colsum_bench);
   m.def("token_sort_bench", &cst::token_sort_bench);

@@ -112,8 +112,10 @@ at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v
                           at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
                           double b1, double b2, double eps, double clip, double gscale,
                           int64_t phase, at::Tensor shadow_meta,
-                          std::vector<at::Tensor> shadow_dst);
-void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tensor> shadow_dst);
+                          std::vector<at::Tensor> shadow_dst, c10::optional<at::Tensor> ema,
+                          double ema_decay);
+void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tensor> shadow_dst,
+                     c10::optional<at::Tensor> swap_with);
 
 // dev_entries.cpp: test and microbenchmark entries
 double lstm_bwd_loop_bench(int64_t R, int64_t H, int64_t T, int64_t iters, at::Tensor phases,

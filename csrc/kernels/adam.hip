@@ -37,6 +37,14 @@
 // so no separate conversion / cat / gather pass runs after the optimizer.
 // Memory-bound: 5 x 4 B read + 3 x 4 B write per parameter (+ 2 B per
 // shadowed parameter).
+//
+// EMA (--ema_decay d > 0): the same pass keeps an exponential moving average
+// of the parameters, e += (1 - d) * (p_new - e) in fp32 (e == p is an exact
+// fixed point), one more 4 B read and write per parameter, skipped with the
+// update.  It is a template switch: adam_update_kernel<false> is the kernel
+// without any of it.  swap_refresh_kernel exchanges the parameters with the
+// EMA (validation decodes the averaged weights) and rewrites the shadows from
+// what ends up in p in the same pass; a second call restores both bit for bit.
 #include "../common.h"
 #include "../launchers.h"
 
@@ -176,21 +184,40 @@ __global__ __launch_bounds__(256) void shadow_refresh_kernel(const float* __rest
     shadow_store(ss, g.off + j, p[g.off + j]);
 }
 
+// One parameter's update.  The roundings are spelled out (no contraction left
+// to the compiler), so that every instantiation of the update kernel computes
+// the same bits: which of the two products of a moment update is fused into
+// the FMA differs between the float4 body and the tail loop (TAIL), exactly
+// as the kernel has always been compiled.
+template <bool TAIL>
 __device__ __forceinline__ void adam_one(float& p, float& m, float& v, float g, float coef,
                                          float lr_bc1, float b1, float b2, float eps,
                                          float inv_sqrt_bc2) {
+#pragma clang fp contract(off)
   g *= coef;
-  m = b1 * m + (1.f - b1) * g;
-  v = b2 * v + (1.f - b2) * g * g;
-  const float denom = sqrtf(v) * inv_sqrt_bc2 + eps;
+  const float g2 = (1.f - b2) * g;
+  if constexpr (TAIL) {
+    m = __builtin_fmaf(1.f - b1, g, b1 * m);
+    v = __builtin_fmaf(g, g2, b2 * v);
+  } else {
+    m = __builtin_fmaf(b1, m, (1.f - b1) * g);
+    v = __builtin_fmaf(b2, v, g * g2);
+  }
+  const float denom = __builtin_fmaf(sqrtf(v), inv_sqrt_bc2, eps);
   p -= lr_bc1 * m / denom;
 }
 
+__device__ __forceinline__ void ema_one(float& e, float p, float one_minus_d) {
+  e += one_minus_d * (p - e);
+}
+
+template <bool EMA>
 __global__ __launch_bounds__(ADAM_THREADS) void adam_update_kernel(
     float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
     float* __restrict__ v, int64_t n, const float* __restrict__ partials, int nparts,
     const bool* __restrict__ skip, float* __restrict__ scal, float* __restrict__ hyper,
-    float b1, float b2, float eps, float clip, float gscale, ShadowSegs ss) {
+    float b1, float b2, float eps, float clip, float gscale, ShadowSegs ss,
+    float* __restrict__ ema, float one_minus_d) {
   __shared__ float sh[ADAM_THREADS / 64];
   __shared__ float s_coef;
   __shared__ int s_skip;
@@ -224,19 +251,54 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_update_kernel(
        i += (int64_t)gridDim.x * ADAM_THREADS) {
     float4 pp = p4[i], mm = m4[i], vv = v4[i];
     const float4 gg = g4[i];
-    adam_one(pp.x, mm.x, vv.x, gg.x, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
-    adam_one(pp.y, mm.y, vv.y, gg.y, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
-    adam_one(pp.z, mm.z, vv.z, gg.z, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
-    adam_one(pp.w, mm.w, vv.w, gg.w, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+    adam_one<false>(pp.x, mm.x, vv.x, gg.x, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+    adam_one<false>(pp.y, mm.y, vv.y, gg.y, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+    adam_one<false>(pp.z, mm.z, vv.z, gg.z, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+    adam_one<false>(pp.w, mm.w, vv.w, gg.w, coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
     p4[i] = pp;
     m4[i] = mm;
     v4[i] = vv;
+    if constexpr (EMA) {
+      float4* e4 = reinterpret_cast<float4*>(ema);
+      float4 ee = e4[i];
+      ema_one(ee.x, pp.x, one_minus_d);
+      ema_one(ee.y, pp.y, one_minus_d);
+      ema_one(ee.z, pp.z, one_minus_d);
+      ema_one(ee.w, pp.w, one_minus_d);
+      e4[i] = ee;
+    }
     if (ss.n > 0) shadow_store4(ss, 4 * i, pp);
   }
   if (blockIdx.x == 0) {
     for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += ADAM_THREADS) {
-      adam_one(p[i], m[i], v[i], g[i], coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+      adam_one<true>(p[i], m[i], v[i], g[i], coef, lr_bc1, b1, b2, eps, inv_sqrt_bc2);
+      if constexpr (EMA) ema_one(ema[i], p[i], one_minus_d);
       if (ss.n > 0) shadow_store(ss, i, p[i]);
+    }
+  }
+}
+
+// p <-> q element by element, and the bf16 shadows of what ends up in p
+// (float4 body, block 0 takes the tail; any n, shadow segments at any offset)
+__global__ __launch_bounds__(ADAM_THREADS) void swap_refresh_kernel(float* __restrict__ p,
+                                                                     float* __restrict__ q,
+                                                                     int64_t n, ShadowSegs ss) {
+  const int64_t n4 = n >> 2;
+  float4* p4 = reinterpret_cast<float4*>(p);
+  float4* q4 = reinterpret_cast<float4*>(q);
+  for (int64_t i = blockIdx.x * (int64_t)ADAM_THREADS + threadIdx.x; i < n4;
+       i += (int64_t)gridDim.x * ADAM_THREADS) {
+    const float4 pp = p4[i], qq = q4[i];
+    p4[i] = qq;
+    q4[i] = pp;
+    if (ss.n > 0) shadow_store4(ss, 4 * i, qq);
+  }
+  if (blockIdx.x == 0) {
+    for (int64_t i = (n4 << 2) + threadIdx.x; i < n; i += ADAM_THREADS) {
+      const float pp = p[i], qq = q[i];
+      p[i] = qq;
+      q[i] = pp;
+      if (ss.n > 0) shadow_store(ss, i, qq);
     }
   }
 }
@@ -244,7 +306,7 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_update_kernel(
 void launch_flat_adam(float* p, const float* g, float* m, float* v, int64_t n, float* partials,
                       const bool* skip, float* scal, float* hyper, float b1, float b2,
                       float eps, float clip, float gscale, int phase, const ShadowSegs& ss,
-                      hipStream_t stream) {
+                      float* ema, float one_minus_d, hipStream_t stream) {
   // (a sharded update: every rank's shard has the same n, so the same
   // number of partials, which the caller all-reduces between phases 1 and 2)
   int blocks = (int)std::min<int64_t>(ADAM_MAX_PARTIALS, std::max<int64_t>(1, (n / 4 + 255) / 256));
@@ -255,9 +317,23 @@ void launch_flat_adam(float* p, const float* g, float* m, float* v, int64_t n, f
   }
   if (phase == 1) return;
   int ublocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n / 4 + 255) / 256));
-  hipLaunchKernelGGL(adam_update_kernel, dim3(ublocks), dim3(ADAM_THREADS), 0, stream, p, g, m,
-                     v, n, partials, blocks, skip, scal, hyper, b1, b2, eps, clip, gscale, ss);
+  if (ema != nullptr)
+    hipLaunchKernelGGL(adam_update_kernel<true>, dim3(ublocks), dim3(ADAM_THREADS), 0, stream, p,
+                       g, m, v, n, partials, blocks, skip, scal, hyper, b1, b2, eps, clip, gscale,
+                       ss, ema, one_minus_d);
+  else
+    hipLaunchKernelGGL(adam_update_kernel<false>, dim3(ublocks), dim3(ADAM_THREADS), 0, stream, p,
+                       g, m, v, n, partials, blocks, skip, scal, hyper, b1, b2, eps, clip, gscale,
+                       ss, ema, one_minus_d);
   post_launch("adam_update_kernel", stream);
+}
+
+void launch_swap_refresh(float* p, float* q, int64_t n, const ShadowSegs& ss,
+                         hipStream_t stream) {
+  const int blocks = (int)std::min<int64_t>(2048, std::max<int64_t>(1, (n / 4 + 255) / 256));
+  hipLaunchKernelGGL(swap_refresh_kernel, dim3(blocks), dim3(ADAM_THREADS), 0, stream, p, q, n,
+                     ss);
+  post_launch("swap_refresh_kernel", stream);
 }
 
 void launch_shadow_refresh(const float* p, const ShadowSegs& ss, hipStream_t stream) {

@@ -164,12 +164,17 @@ struct ShadowSegs {
   ShadowSeg s[SHADOW_MAX_SEGS];
   int n;
 };
-// hyper (device): [lr, step before, skipped count, step after] (adam.hip)
+// hyper (device): [lr, step before, skipped count, step after] (adam.hip);
+// ema: nullptr = no EMA (the update kernel's instantiation without it), else
+// e += one_minus_d * (p_new - e) in the update pass
 void launch_flat_adam(float* p, const float* g, float* m, float* v, int64_t n, float* partials,
                       const bool* skip, float* scal, float* hyper, float b1, float b2,
                       float eps, float clip, float gscale, int phase, const ShadowSegs& ss,
-                      hipStream_t stream);
+                      float* ema, float one_minus_d, hipStream_t stream);
 void launch_shadow_refresh(const float* p, const ShadowSegs& ss, hipStream_t stream);
+// p <-> q (n fp32 each, 16-byte aligned, disjoint) + the shadows of the new p
+void launch_swap_refresh(float* p, float* q, int64_t n, const ShadowSegs& ss,
+                         hipStream_t stream);
 
 // vocab.hip
 enum SelModeHost : int { SEL_GT_H = 0, SEL_SAMPLE_H = 1, SEL_GREEDY_H = 2, SEL_SS_H = 3 };

@@ -615,7 +615,8 @@ at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v
                           at::Tensor partials, at::Tensor scal, at::Tensor skip, at::Tensor hyper,
                           double b1, double b2, double eps, double clip, double gscale,
                           int64_t phase, at::Tensor shadow_meta,
-                          std::vector<at::Tensor> shadow_dst) {
+                          std::vector<at::Tensor> shadow_dst, c10::optional<at::Tensor> ema,
+                          double ema_decay) {
   check_cuda(p, "p");
   for (auto* t : {&g, &m, &v}) {
     check_cuda(*t, "adam operand");
@@ -628,19 +629,50 @@ at::Tensor flat_adam_step(at::Tensor p, at::Tensor g, at::Tensor m, at::Tensor v
   const ShadowSegs ss = make_shadow_segs(shadow_meta, shadow_dst);
   for (int k = 0; k < ss.n; ++k)
     TORCH_CHECK(ss.s[k].off >= 0 && ss.s[k].off + ss.s[k].n <= p.numel(), "shadow range");
+  // parameter EMA kept by the update pass (undefined or empty: off)
+  float* ema_ptr = nullptr;
+  float one_minus_d = 0.f;
+  if (ema.has_value() && ema->defined() && ema->numel() > 0) {
+    check_cuda(*ema, "ema");
+    TORCH_CHECK(ema->scalar_type() == at::kFloat && ema->numel() == p.numel(),
+                "ema must be fp32 with the numel of p");
+    TORCH_CHECK(ema_decay >= 0.0 && ema_decay < 1.0, "ema_decay must be in [0, 1), got ",
+                ema_decay);
+    ema_ptr = ema->data_ptr<float>();
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(ema_ptr) % 16 == 0, "ema must be 16-byte aligned");
+    one_minus_d = (float)(1.0 - ema_decay);
+  }
   launch_flat_adam(p.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
                    v.data_ptr<float>(), p.numel(), partials.data_ptr<float>(),
                    skip.data_ptr<bool>(), scal.data_ptr<float>(), hyper.data_ptr<float>(),
                    (float)b1, (float)b2, (float)eps, (float)clip, (float)gscale, (int)phase, ss,
-                   cur_stream());
+                   ema_ptr, one_minus_d, cur_stream());
   return scal.narrow(0, 0, 1).squeeze(0);
 }
 
-void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tensor> shadow_dst) {
+// swap_with given: p and swap_with are exchanged element by element and the
+// shadows are written from the new p, in one pass (FlatAdam.swap_ema)
+void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tensor> shadow_dst,
+                     c10::optional<at::Tensor> swap_with) {
   check_cuda(p, "p");
   const ShadowSegs ss = make_shadow_segs(shadow_meta, shadow_dst);
   for (int k = 0; k < ss.n; ++k)
     TORCH_CHECK(ss.s[k].off >= 0 && ss.s[k].off + ss.s[k].n <= p.numel(), "shadow range");
+  if (swap_with.has_value() && swap_with->defined()) {
+    const at::Tensor& q = *swap_with;
+    check_cuda(q, "swap_with");
+    TORCH_CHECK(p.scalar_type() == at::kFloat && q.scalar_type() == at::kFloat &&
+                    q.numel() == p.numel(),
+                "swap_with must be fp32 with the numel of p");
+    float* pp = p.data_ptr<float>();
+    float* qq = q.data_ptr<float>();
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(pp) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>(qq) % 16 == 0,
+                "p and swap_with must be 16-byte aligned");
+    TORCH_CHECK(pp + p.numel() <= qq || qq + q.numel() <= pp, "p and swap_with overlap");
+    launch_swap_refresh(pp, qq, p.numel(), ss, cur_stream());
+    return;
+  }
   launch_shadow_refresh(p.data_ptr<float>(), ss, cur_stream());
 }
 

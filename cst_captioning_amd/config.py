@@ -39,6 +39,17 @@ def mbr_mix_arg(spec):
     return spec
 
 
+def ema_decay_arg(spec):
+    """``--ema_decay``: a float in [0, 1); 0 = no EMA."""
+    try:
+        d = float(spec)
+    except ValueError:
+        raise argparse.ArgumentTypeError('not a number: %r' % spec)
+    if not 0.0 <= d < 1.0:  # (NaN fails the comparison too)
+        raise argparse.ArgumentTypeError('--ema_decay must be in [0, 1), got %r' % spec)
+    return d
+
+
 def build_parser():
     p = argparse.ArgumentParser(
         description='MI355X-native consensus/self-critical video captioning trainer')
@@ -190,6 +201,11 @@ def build_parser():
         help='data-parallel update: all-reduce the fp32 gradient and run Adam on the whole '
              'buffer on every rank (default), or reduce-scatter -> Adam on this rank\'s '
              '1/N shard (fp32 moments kept for the shard only) -> all-gather the parameters')
+    add('--ema_decay', type=ema_decay_arg, default=0.0, metavar='D',
+        help='keep an exponential moving average of the parameters, e += (1 - D) (p - e) in '
+             'the fused Adam pass, and validate / select / save the best checkpoint with it '
+             '(the _last.pth sidecar keeps the live weights, the EMA in its optimizer state).  '
+             '0 (default): off')
     add('--profile_phases', type=int, default=0, help='log per-phase HIP-event timings')
     return p
 

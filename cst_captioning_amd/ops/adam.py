@@ -21,6 +21,12 @@ advance the step; skips are counted on the device.  The math is PyTorch's Adam:
 ``denom = sqrt(v) / sqrt(1 - b2^t) + eps``,
 ``p -= lr / (1 - b1^t) * m / denom``.
 
+EMA (``ema_decay`` d > 0): the update pass also keeps an exponential moving
+average of the parameters, ``e += (1 - d) * (p_new - e)`` in fp32, skipped
+exactly when the update is; :meth:`swap_ema` exchanges it with the parameters
+(and rewrites the bf16 shadows) for validation and checkpoint selection.
+``ema_decay = 0`` (default): no buffer, the update kernel without any of it.
+
 Without the HIP extension (CPU) the same math runs as torch ops.
 """
 import math
@@ -31,7 +37,11 @@ from .. import _ext
 
 
 class FlatAdam:
-    def __init__(self, bucket, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_clip=0.25):
+    def __init__(self, bucket, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, grad_clip=0.25,
+                 ema_decay=0.0):
+        ema_decay = float(ema_decay)
+        if not 0.0 <= ema_decay < 1.0:  # (NaN fails the comparison too)
+            raise ValueError('ema_decay must be in [0, 1), got %r' % ema_decay)
         self.bucket = bucket
         self.lr = lr
         self.betas = betas
@@ -42,6 +52,11 @@ class FlatAdam:
         self.grad_scale = 1.0
         self.exp_avg = torch.zeros_like(bucket.data)
         self.exp_avg_sq = torch.zeros_like(bucket.data)
+        # EMA of the parameters, updated by the update pass (None: off)
+        self.ema_decay = ema_decay
+        self.ema = bucket.data.clone() if ema_decay > 0 else None
+        # fp32(1 - d), the factor the kernel and the torch path both apply
+        self._one_minus_d = float(torch.tensor(1.0 - ema_decay, dtype=torch.float64).float())
         self.param_groups = [{'lr': lr}]  # for adjust_learning_rate()
         self.last_norm = None
         self._use_hip = _ext.available() and bucket.data.is_cuda
@@ -61,6 +76,36 @@ class FlatAdam:
     def set_shadows(self, meta, dsts):
         """bf16 shadow copies the update pass writes (see csrc/kernels/adam.hip)."""
         self._shadow = (meta, list(dsts))
+
+    def reset_ema(self):
+        """EMA := the current parameters (after weights were loaded)."""
+        if self.ema is not None:
+            self.ema.copy_(self.bucket.data)
+
+    @torch.no_grad()
+    def swap_ema(self):
+        """Exchange the parameters with their EMA; the bf16 shadows follow the
+        new parameters.  A second call restores everything bit for bit.  Call
+        between graph replays, never inside a capture."""
+        if self.ema is None:
+            raise RuntimeError('swap_ema() without an EMA (ema_decay = 0)')
+        p = self.bucket.data
+        if self._use_hip:
+            _ext.ops().refresh_shadows(p, *self._shadow, self.ema)
+            return
+        tmp = p.clone()
+        p.copy_(self.ema)
+        self.ema.copy_(tmp)
+
+    def _ema_args(self, lo=None, hi=None):
+        if self.ema is None:
+            return ()
+        return (self.ema if lo is None else self.ema[lo:hi], self.ema_decay)
+
+    def _ema_torch(self, e, p, keep):
+        """torch path: the kernel's expression on the updated ``p``, under
+        the same ``keep`` mask (0-dim bool)."""
+        e.copy_(torch.where(keep, e + self._one_minus_d * (p - e), e))
 
     def sync_lr(self):
         """Publish ``param_groups[0]['lr']`` to the device (no-op if unchanged).
@@ -88,7 +133,7 @@ class FlatAdam:
                 p, g, self.exp_avg, self.exp_avg_sq, self._partials, self._scal,
                 skip if skip is not None else self._no_skip, self._hyper,
                 float(b1), float(b2), float(self.eps), float(self.grad_clip),
-                float(self.grad_scale), 0, *self._shadow)
+                float(self.grad_scale), 0, *self._shadow, *self._ema_args())
             return self.last_norm
         h = self._hyper
         h[1].copy_(h[3])
@@ -111,6 +156,8 @@ class FlatAdam:
         self.exp_avg.copy_(torch.where(keep, m_new, self.exp_avg))
         self.exp_avg_sq.copy_(torch.where(keep, v_new, self.exp_avg_sq))
         p.copy_(torch.where(keep, p - upd, p))
+        if self.ema is not None:
+            self._ema_torch(self.ema, p, keep)
         h[3].copy_(torch.where(keep, t.float(), h[1]))
         h[2].add_(bad.float())
         return norm
@@ -144,7 +191,7 @@ class FlatAdam:
             any_skip = self._partials[1024] > 0
             self.last_norm = ops.flat_adam_step(
                 p, gshard, m, v, self._partials, self._scal, any_skip, self._hyper, *args, 2,
-                torch.empty(0, dtype=torch.int64), [])
+                torch.empty(0, dtype=torch.int64), [], *self._ema_args(lo, hi))
             return self.last_norm
         h = self._hyper
         h[1].copy_(h[3])
@@ -167,13 +214,15 @@ class FlatAdam:
         m.copy_(torch.where(keep, m_new, m))
         v.copy_(torch.where(keep, v_new, v))
         p.copy_(torch.where(keep, p - upd, p))
+        if self.ema is not None:
+            self._ema_torch(self.ema[lo:hi], p, keep)
         h[3].copy_(torch.where(keep, t.float(), h[1]))
         h[2].add_(bad.float())
         return norm
 
     def consolidate(self, ctx):
-        """Sharded update: gather every rank's moment shards, so the full
-        Adam state is on every rank (checkpoints).  Collective."""
+        """Sharded update: gather every rank's moment (and EMA) shards, so the
+        full Adam state is on every rank (checkpoints).  Collective."""
         import torch.distributed as dist
         if not (self.bucket.sharded and ctx.enabled):
             return
@@ -181,6 +230,17 @@ class FlatAdam:
         for buf in (self.exp_avg, self.exp_avg_sq):
             mine = buf[lo:hi].clone()
             dist.all_gather_into_tensor(buf, mine)
+        self.gather_ema(ctx)
+
+    def gather_ema(self, ctx):
+        """Sharded update: every rank's EMA shard into the full EMA buffer
+        (before :meth:`swap_ema`).  Collective; no-op otherwise."""
+        import torch.distributed as dist
+        if self.ema is None or not (self.bucket.sharded and ctx.enabled):
+            return
+        lo, hi = self.bucket.shard_range(ctx.rank)
+        mine = self.ema[lo:hi].clone()
+        dist.all_gather_into_tensor(self.ema, mine)
 
     @property
     def step_count(self):
@@ -196,10 +256,14 @@ class FlatAdam:
         return int(self._hyper[3].item())
 
     def state_dict(self):
-        return {'step': self._steps(), 'exp_avg': self.exp_avg,
-                'exp_avg_sq': self.exp_avg_sq, 'lr': self.param_groups[0]['lr'],
-                'betas': self.betas, 'eps': self.eps,
-                'skipped': int(self._hyper[2].item())}
+        s = {'step': self._steps(), 'exp_avg': self.exp_avg,
+             'exp_avg_sq': self.exp_avg_sq, 'lr': self.param_groups[0]['lr'],
+             'betas': self.betas, 'eps': self.eps,
+             'skipped': int(self._hyper[2].item())}
+        if self.ema is not None:  # (a default optimizer's keys stay as they were)
+            s['ema'] = self.ema
+            s['ema_decay'] = self.ema_decay
+        return s
 
     def load_state_dict(self, s):
         self.exp_avg.copy_(s['exp_avg'])
@@ -211,3 +275,9 @@ class FlatAdam:
         self._hyper[0].fill_(float(s['lr']))
         if self._use_hip:
             self._lr_synced = float(s['lr'])
+        if self.ema is not None:
+            # (the parameters are loaded before the optimizer state)
+            if s.get('ema') is not None:
+                self.ema.copy_(s['ema'])
+            else:
+                self.reset_ema()

@@ -21,6 +21,7 @@ so the expanded rows are identical), gradients live in one flat bucket that
 is all-reduced once per step (DP), and clip + Adam is one fused kernel.
 Host synchronisation happens only at log / eval time.
 """
+import contextlib
 import json
 import logging
 import math
@@ -99,6 +100,38 @@ def check_val_scorer(opt, loader):
                          'built (python setup.py build_ext --inplace)')
 
 
+_GREEDY_STREAMS = {}
+
+
+def greedy_stream(device, engine=None):
+    """The stream of the concurrent greedy baseline: ONE per device, shared by
+    every trainer of the process.  torch.cuda.Stream() hands out the 32 streams
+    of a pool round-robin, so a stream per trainer came back, every 32nd time,
+    as the very stream of the engine's X = E W side work (or of its gate-table
+    prefetch, or the graph capture stream) -- and X launched on the greedy
+    stream is the fork / join shape that crashes hipStreamEndCapture (see
+    rl_loss).  Which trainer was hit depended on how many streams the process
+    had created before.  The shared stream is also checked against those
+    streams when it is created."""
+    dev = torch.device(device)
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    if key not in _GREEDY_STREAMS:
+        aux = getattr(engine, '_aux', None)
+        avoid = [torch.cuda.current_stream(dev), torch.cuda.default_stream(dev),
+                 getattr(torch.cuda.graph, 'default_capture_stream', None)]
+        if aux is not None:
+            avoid += [aux.ptab_stream, aux.x_stream]
+        taken = {s.cuda_stream for s in avoid if s is not None}
+        for _ in range(64):
+            s = torch.cuda.Stream(device=dev)
+            if s.cuda_stream not in taken:
+                break
+        else:
+            raise RuntimeError('no stream distinct from the engine\'s side streams')
+        _GREEDY_STREAMS[key] = s
+    return _GREEDY_STREAMS[key]
+
+
 class Trainer:
     def __init__(self, opt, model, train_loader, val_loader=None, ctx=None, engine=None):
         from ..parallel import DistContext
@@ -166,7 +199,11 @@ class Trainer:
             betas, eps = (opt.optim_alpha, opt.optim_beta), opt.optim_epsilon
         else:
             betas, eps = (0.9, 0.999), 1e-8  # train.py:492 ignores --optim_*
-        self.optimizer = FlatAdam(self.bucket, opt.learning_rate, betas, eps, opt.grad_clip)
+        self.optimizer = FlatAdam(self.bucket, opt.learning_rate, betas, eps, opt.grad_clip,
+                                  ema_decay=getattr(opt, 'ema_decay', 0.0))
+        if self.optimizer.ema is not None:
+            logger.info('EMA of the parameters: decay %g (validation, the best score and the '
+                        'best checkpoint use the averaged weights)', self.optimizer.ema_decay)
         self.optimizer.grad_scale = self.bucket.grad_scale(self.ctx)
         if engine is not None:
             engine.attach_optimizer(self)
@@ -275,7 +312,7 @@ class Trainer:
             if getattr(self, '_side_stream', None) is None:
                 # (a high-priority stream for the greedy decode measured 4.5 ->
                 # 8.7 ms per step: the queue priority throttles the rollout)
-                self._side_stream = torch.cuda.Stream(device=self.device)
+                self._side_stream = greedy_stream(self.device, self.engine)
                 self._ev_inputs = torch.cuda.Event()
                 self._ev_greedy = torch.cuda.Event()
             side = self._side_stream
@@ -634,6 +671,29 @@ class Trainer:
         logger.info('captured the training step as a HIP graph (%s)',
                     'two graphs around the all-reduce' if g_b is not None else 'one graph')
 
+    # ---------------------------------------------------------------- EMA ---
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside: the model's parameters, the engine's bf16 shadows and all it
+        derives from them hold the EMA of the weights (--ema_decay); on exit
+        the live weights are back, bit for bit.  No-op without an EMA.  Enter
+        between graph replays, never inside a capture.  Collective under
+        --dp_update sharded (the EMA shards are gathered first)."""
+        o = self.optimizer
+        if o.ema is None:
+            yield
+            return
+        o.gather_ema(self.ctx)
+        o.swap_ema()
+        if self.engine is not None:
+            self.engine.after_step()
+        try:
+            yield
+        finally:
+            o.swap_ema()
+            if self.engine is not None:
+                self.engine.after_step()
+
     # --------------------------------------------------------------- loop ---
     def resume(self):
         opt = self.opt
@@ -663,6 +723,7 @@ class Trainer:
             logger.info('Loading state from: %s', path)
             s = ckpt.load_checkpoint(path, map_location=self.device)
             self.model.load_state_dict(s['model'])
+            self.optimizer.reset_ema()  # warm start: the average starts at the loaded weights
             self.infos = s['infos']
             self.infos['start_epoch'] = self.infos['epoch']
             return True
@@ -727,12 +788,16 @@ class Trainer:
                 self._save_last(checked=False)
             if (self.val_loader is not None and infos['epoch'] >= opt.save_checkpoint_from
                     and infos['epoch'] % opt.save_checkpoint_every == 0 and not checked):
-                results = self.validate(self.val_loader)
-                if self.ctx.is_main:
-                    logger.info('Validation output: %s',
-                                json.dumps(results['scores'], indent=4, sort_keys=True))
-                infos.update(results['scores'])
-                self.check_model()
+                # --ema_decay: the averaged weights are validated, selected and
+                # written as the best checkpoint's model; the sidecar below
+                # keeps the live ones (the EMA in its optimizer state)
+                with self.ema_weights():
+                    results = self.validate(self.val_loader)
+                    if self.ctx.is_main:
+                        logger.info('Validation output: %s',
+                                    json.dumps(results['scores'], indent=4, sort_keys=True))
+                    infos.update(results['scores'])
+                    self.check_model()
                 checked = True
                 # re-save with the validated best score / epoch and history
                 self._save_last(checked=True)
