@@ -396,8 +396,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bs"), py::arg("drop_p"), py::arg("rng"), py::arg("idx") = py::none(),
         py::arg("C") = 1);
   m.def("scst_loss_forward", &cst::scst_loss_forward);
-  m.def("cst_loss_forward", &cst::cst_loss_forward);
-  m.def("scst_loss_backward", &cst::scst_loss_backward);
+  // objective 1 risk / 2 softmax_margin / 3 multi_margin: the group loss over each video's S
+  // rows (bref, k unused), a 4th result = the row weights scst_loss_backward's row_weight takes
+  m.def("cst_loss_forward", &cst::cst_loss_forward, py::arg("seq"), py::arg("lp"),
+        py::arg("scores"), py::arg("bref"), py::arg("S"), py::arg("k"), py::arg("objective") = 0,
+        py::arg("alpha") = 1.0, py::arg("cost_scale") = 1.0);
+  m.def("scst_loss_backward", &cst::scst_loss_backward, py::arg("seq"), py::arg("reward"),
+        py::arg("out"), py::arg("dloss"), py::arg("row_weight") = py::none());
   m.def("xe_loss_forward", &cst::xe_loss_forward);
   m.def("xe_loss_backward", &cst::xe_loss_backward);
   m.def("featpool_backward", &cst::featpool_backward, py::arg("dout"), py::arg("out"),

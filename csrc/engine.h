@@ -82,13 +82,14 @@ std::vector<at::Tensor> featpool_backward(at::Tensor dout, at::Tensor out,
                                           std::vector<at::Tensor> outs,
                                           c10::optional<at::Tensor> idx, int64_t C);
 std::vector<at::Tensor> cst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor scores,
-                                         at::Tensor bref, int64_t S, int64_t k);
+                                         at::Tensor bref, int64_t S, int64_t k, int64_t objective,
+                                         double alpha, double cost_scale);
 std::vector<at::Tensor> scst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor sample,
                                           at::Tensor greedy);
 std::vector<at::Tensor> xe_loss_forward(at::Tensor labels, at::Tensor lp, int64_t off);
 at::Tensor xe_loss_backward(at::Tensor cnt, at::Tensor out, at::Tensor dloss, int64_t T);
 at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
-                              at::Tensor dloss);
+                              at::Tensor dloss, c10::optional<at::Tensor> row_weight);
 at::Tensor cider_score(at::Tensor hyps, at::Tensor hyp_video, std::map<std::string, at::Tensor> t,
                        double log_ref_len, int64_t use_eos, bool clipped,
                        c10::optional<at::Tensor> exclude, int64_t group);

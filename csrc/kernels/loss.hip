@@ -179,6 +179,149 @@ void launch_scst_loss_bwd(const int64_t* seq, const float* reward, const float* 
   post_launch("scst_loss_bwd_kernel", stream);
 }
 
+// Group objectives (--rl_objective; models/criteria.py GroupCriterion): the
+// sequence-level structured losses over each video's S rollout rows --
+// expected risk (Shen et al. 2016), softmax-margin and multi-margin (Edunov
+// et al. 2018) -- on the length-normalised scores s_i = alpha sum(m lp) / n_i
+// with costs c_i = kappa (max_j r_j - r_i), i* the first row attaining the
+// maximum.  dL_v/ds_i =: g_i is constant over a row's tokens, so the forward
+// leaves the row weight w_i = g_i alpha / (B n_i) and the backward is
+// dlp = w_i * mask * dloss, the REINFORCE backward's shape.
+//
+// One wavefront per video, four per workgroup: per row the lanes stride over
+// T and a wave reduction leaves s_i, n_i in lane i; the group maximum, softmax
+// and logsumexp are wave reductions over lanes < S (maximum subtracted,
+// accurate expf / logf).  Per-workgroup partials {sum L_v, sum r, sum b_v,
+// sum mask} go through total_of_partials: workgroup order, bit-equal runs.
+constexpr int GL_VIDS = 4;   // videos (waves) per workgroup
+constexpr int GL_CHUNK = 8;  // rows of a video reduced together
+int group_loss_ws_ints(int B) { return 4 * ((B + GL_VIDS - 1) / GL_VIDS) + 64; }
+
+__global__ __launch_bounds__(256) void group_loss_fwd_kernel(
+    const int64_t* __restrict__ seq, const float* __restrict__ lp, int B, int T,
+    const float* __restrict__ scores, GroupObj go, float* __restrict__ reward,
+    float* __restrict__ wrow, float* __restrict__ out, float* __restrict__ loss,
+    int* __restrict__ ws) {
+  __shared__ float sh[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int v = blockIdx.x * GL_VIDS + w, S = go.S;
+  float Lv = 0.f, rsum = 0.f, bv = 0.f, msum = 0.f;  // (wave-uniform; an empty wave adds 0)
+  if (v < B) {
+    const bool in = lane < S;
+    // lane i: masked log-prob sum and token count of row i of the video
+    // (GL_CHUNK rows at a time: their loads are in flight together, the
+    // reductions behind them interleave)
+    float sl = 0.f, n = 1.f;
+    for (int i0 = 0; i0 < S; i0 += GL_CHUNK) {
+      float a[GL_CHUNK], c[GL_CHUNK];
+#pragma unroll
+      for (int j = 0; j < GL_CHUNK; ++j) {
+        a[j] = c[j] = 0.f;
+        if (i0 + j < S) {
+          const int64_t* srow = seq + ((int64_t)v * S + i0 + j) * T;
+          const float* lrow = lp + ((int64_t)v * S + i0 + j) * T;
+          for (int t = lane; t < T; t += 64) {
+            const float m = (t == 0 || srow[t - 1] > 0) ? 1.f : 0.f;
+            a[j] += lrow[t] * m;
+            c[j] += m;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < GL_CHUNK; ++j) {
+        const float as = wave_sum(a[j]), cs = wave_sum(c[j]);
+        if (lane == i0 + j && i0 + j < S) {
+          sl = as;
+          n = cs;
+        }
+      }
+    }
+    const float NEG = -INFINITY;
+    const float r = in ? scores[(int64_t)v * S + lane] : 0.f;
+    const float s = go.alpha * sl / n;
+    const float rmax = wave_max(in ? r : NEG);
+    const unsigned long long at_max = __ballot(in && r == rmax);
+    const int istar = at_max != 0ull ? __builtin_ctzll(at_max) : 0;  // (0: every score NaN)
+    const float c = go.kappa * (rmax - r);
+    float g;  // dL_v / ds_i
+    if (go.kind == GROUP_RISK) {
+      const float smax = wave_max(in ? s : NEG);
+      const float e = in ? expf(s - smax) : 0.f;
+      const float q = e / wave_sum(e);
+      Lv = wave_sum(q * c);
+      bv = wave_sum(q * r);
+      g = q * (c - Lv);
+    } else if (go.kind == GROUP_SOFTMAX_MARGIN) {
+      const float z = s + c;
+      const float zmax = wave_max(in ? z : NEG);
+      const float e = in ? expf(z - zmax) : 0.f;
+      const float Z = wave_sum(e);
+      Lv = zmax + logf(Z) - __shfl(s, istar, 64);
+      bv = rmax;
+      g = e / Z - (lane == istar ? 1.f : 0.f);
+    } else {
+      // multi-margin: h_j > 0 strictly (h_{i*} = 0 is never active)
+      const float h = c - __shfl(s, istar, 64) + s;
+      const bool act = in && lane != istar && h > 0.f;
+      const float nact = wave_sum(act ? 1.f : 0.f);
+      Lv = wave_sum(act ? h : 0.f) / (float)S;
+      bv = rmax;
+      g = act ? 1.f / (float)S : (lane == istar ? -nact / (float)S : 0.f);
+    }
+    rsum = wave_sum(r);
+    msum = wave_sum(in ? n : 0.f);
+    if (in) {
+      reward[(int64_t)v * S + lane] = r - bv;
+      wrow[(int64_t)v * S + lane] = g * go.alpha / ((float)B * n);
+    }
+  }
+  const bool first = lane == 0;
+  Lv = block_sum_256(first ? Lv : 0.f, sh);
+  rsum = block_sum_256(first ? rsum : 0.f, sh);
+  bv = block_sum_256(first ? bv : 0.f, sh);
+  msum = block_sum_256(first ? msum : 0.f, sh);
+  float a[4];
+  if (!total_of_partials(Lv, rsum, bv, msum, ws, a)) return;
+  if (threadIdx.x == 0) {
+    out[0] = a[0] / (float)B;
+    loss[0] = out[0];
+    out[1] = a[1] / ((float)B * (float)S);
+    out[2] = a[2] / (float)B;
+    out[3] = a[3];
+    ws[0] = 0;  // re-arm for the next launch (stream-ordered)
+  }
+}
+
+// dlp = w[row] * mask * dloss
+__global__ __launch_bounds__(256) void group_loss_bwd_kernel(const int64_t* __restrict__ seq,
+                                                             const float* __restrict__ wrow,
+                                                             const float* __restrict__ dloss,
+                                                             int R, int T,
+                                                             float* __restrict__ dlp) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (int64_t)R * T) return;
+  const int r = (int)(i / T), t = (int)(i % T);
+  const float m = (t == 0 || seq[i - 1] > 0) ? 1.f : 0.f;
+  dlp[i] = wrow[r] * m * dloss[0];
+}
+
+void launch_group_loss_fwd(const int64_t* seq, const float* lp, int R, int T, const float* scores,
+                           GroupObj go, float* reward, float* w, float* out, float* loss, int* ws,
+                           hipStream_t stream) {
+  const int B = R / go.S;
+  hipLaunchKernelGGL(group_loss_fwd_kernel, dim3((B + GL_VIDS - 1) / GL_VIDS), dim3(256), 0,
+                     stream, seq, lp, B, T, scores, go, reward, w, out, loss, ws);
+  post_launch("group_loss_fwd_kernel", stream);
+}
+
+void launch_group_loss_bwd(const int64_t* seq, const float* w, const float* dloss, int R, int T,
+                           float* dlp, hipStream_t stream) {
+  const int64_t n = (int64_t)R * T;
+  hipLaunchKernelGGL(group_loss_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                     stream, seq, w, dloss, R, T, dlp);
+  post_launch("group_loss_bwd_kernel", stream);
+}
+
 // XE (CrossEntropyCriterion on the gathered GT log-probs, models/criteria.py,
 // with the loader's masks, dataloader.py:158-163 / data/dataset.py gather):
 // the mask of label row r covers positions j < nnz(labels[r]) + 1; the

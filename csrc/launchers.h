@@ -553,6 +553,26 @@ void launch_scst_loss_fwd(const int64_t* seq, const float* lp, int R, int T, con
                           int* ws, CstBase cb, hipStream_t stream);
 void launch_scst_loss_bwd(const int64_t* seq, const float* reward, const float* out,
                           const float* dloss, int R, int T, float* dlp, hipStream_t stream);
+// Group objectives over each video's S rollout rows (--rl_objective): expected
+// risk, softmax-margin, multi-margin on the length-normalised sequence scores
+// s_i = alpha * sum(mask lp) / n_i with costs kappa * (max score - score_i).
+// Forward: reward (R) = score - the video's logged baseline, w (R) = the row
+// weight dL/ds_i * alpha / (B n_i), out = {loss, mean score, mean baseline,
+// sum mask}; backward: dlp = w * mask * dloss.  ws: group_loss_ws_ints(R / S)
+// ints, zero before the first launch (the kernel re-arms its ticket)
+enum GroupObjective { GROUP_RISK = 1, GROUP_SOFTMAX_MARGIN = 2, GROUP_MULTI_MARGIN = 3 };
+struct GroupObj {
+  int kind;     // GroupObjective
+  int S;        // rows per video, 2 <= S <= 64, dividing R
+  float alpha;  // scale of the sequence scores, > 0
+  float kappa;  // scale of the costs, >= 0
+};
+int group_loss_ws_ints(int B);
+void launch_group_loss_fwd(const int64_t* seq, const float* lp, int R, int T, const float* scores,
+                           GroupObj go, float* reward, float* w, float* out, float* loss, int* ws,
+                           hipStream_t stream);
+void launch_group_loss_bwd(const int64_t* seq, const float* w, const float* dloss, int R, int T,
+                           float* dlp, hipStream_t stream);
 // XE criterion with the loader's caption masks computed from the label rows
 // (R x L int64): cnt (R) = counted log-probs per row, out = {loss, sum mask};
 // ws as for the SCST loss

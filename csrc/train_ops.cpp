@@ -158,10 +158,38 @@ std::vector<at::Tensor> scst_loss_forward(at::Tensor seq, at::Tensor lp, at::Ten
 // rewarded rows, S rows per video (R % S == 0, S <= 64); bref: (R) GT
 // consensus scores (scb_baseline 1) or empty (scb_baseline 2: the scores
 // themselves); k = scb_captions (0: reward = score) -> {loss, out, reward}
+//
+// objective != 0 (--rl_objective: GroupObjective of launchers.h): the group
+// loss over each video's S rows instead, bref and k unused -> {loss, out,
+// reward, w} with w (R) the row weights scst_loss_backward takes
 std::vector<at::Tensor> cst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tensor scores,
-                                         at::Tensor bref, int64_t S, int64_t k) {
+                                         at::Tensor bref, int64_t S, int64_t k, int64_t objective,
+                                         double alpha, double cost_scale) {
   for (auto* t : {&seq, &lp, &scores}) check_cuda(*t, "cst_loss operand");
   const int64_t R = seq.size(0), T = seq.size(1);
+  if (objective != 0) {
+    TORCH_CHECK(objective >= GROUP_RISK && objective <= GROUP_MULTI_MARGIN,
+                "group_loss: objective 1 (risk), 2 (softmax_margin) or 3 (multi_margin)");
+    TORCH_CHECK(seq.dim() == 2 && lp.dim() == 2 && seq.scalar_type() == at::kLong &&
+                    lp.scalar_type() == at::kFloat && lp.size(0) == R && lp.size(1) == T &&
+                    T >= 1 && scores.scalar_type() == at::kFloat && scores.numel() == R,
+                "group_loss: seq / lp (R, T), T >= 1, scores (R) fp32");
+    TORCH_CHECK(S >= 2 && S <= 64 && R > 0 && R % S == 0,
+                "group_loss: 2 <= S <= 64 rows per video, dividing R (got S = ", S, ", R = ", R,
+                ")");
+    TORCH_CHECK(std::isfinite(alpha) && alpha > 0 && std::isfinite(cost_scale) && cost_scale >= 0,
+                "group_loss: alpha finite and > 0, cost_scale finite and >= 0");
+    auto f32 = lp.options();
+    at::Tensor out = at::empty({4}, f32), reward = at::empty({R}, f32), loss = at::empty({}, f32);
+    at::Tensor w = at::empty({R}, f32);
+    at::Tensor ws = at::zeros({group_loss_ws_ints((int)(R / S))}, f32.dtype(at::kInt));
+    launch_group_loss_fwd(seq.data_ptr<int64_t>(), lp.data_ptr<float>(), (int)R, (int)T,
+                          scores.data_ptr<float>(),
+                          GroupObj{(int)objective, (int)S, (float)alpha, (float)cost_scale},
+                          reward.data_ptr<float>(), w.data_ptr<float>(), out.data_ptr<float>(),
+                          loss.data_ptr<float>(), ws.data_ptr<int>(), cur_stream());
+    return {loss, out, reward, w};
+  }
   const bool has_ref = bref.defined() && bref.numel() > 0;
   TORCH_CHECK(seq.scalar_type() == at::kLong && lp.scalar_type() == at::kFloat &&
                   lp.size(0) == R && lp.size(1) == T && scores.scalar_type() == at::kFloat &&
@@ -183,12 +211,24 @@ std::vector<at::Tensor> cst_loss_forward(at::Tensor seq, at::Tensor lp, at::Tens
   return {loss, out, reward};
 }
 
+// row_weight (R): the group loss's row weights -- dlp = row_weight * mask *
+// dloss, reward and out unused
 at::Tensor scst_loss_backward(at::Tensor seq, at::Tensor reward, at::Tensor out,
-                              at::Tensor dloss) {
+                              at::Tensor dloss, c10::optional<at::Tensor> row_weight) {
   for (auto* t : {&seq, &reward, &out, &dloss}) check_cuda(*t, "scst_loss operand");
   TORCH_CHECK(dloss.scalar_type() == at::kFloat && dloss.numel() == 1, "dloss: fp32 scalar");
   const int64_t R = seq.size(0), T = seq.size(1);
   at::Tensor dlp = at::empty({R, T}, reward.options());
+  if (row_weight.has_value()) {
+    const at::Tensor& w = *row_weight;
+    check_cuda(w, "group_loss row weights");
+    TORCH_CHECK(seq.dim() == 2 && seq.scalar_type() == at::kLong &&
+                    w.scalar_type() == at::kFloat && w.numel() == R,
+                "group_loss backward: seq (R, T) int64, row weights (R) fp32");
+    launch_group_loss_bwd(seq.data_ptr<int64_t>(), w.data_ptr<float>(), dloss.data_ptr<float>(),
+                          (int)R, (int)T, dlp.data_ptr<float>(), cur_stream());
+    return dlp;
+  }
   launch_scst_loss_bwd(seq.data_ptr<int64_t>(), reward.data_ptr<float>(), out.data_ptr<float>(),
                        dloss.data_ptr<float>(), (int)R, (int)T, dlp.data_ptr<float>(),
                        cur_stream());

@@ -50,6 +50,33 @@ def ema_decay_arg(spec):
     return d
 
 
+RL_OBJECTIVES = ('reinforce', 'risk', 'softmax_margin', 'multi_margin')
+
+
+def _finite_float(spec):
+    try:
+        x = float(spec)
+    except ValueError:
+        raise argparse.ArgumentTypeError('not a number: %r' % spec)
+    return x if x == x and abs(x) != float('inf') else None
+
+
+def rl_alpha_arg(spec):
+    """``--rl_alpha``: a finite float > 0."""
+    a = _finite_float(spec)
+    if a is None or not a > 0.0:
+        raise argparse.ArgumentTypeError('--rl_alpha must be finite and > 0, got %r' % spec)
+    return a
+
+
+def rl_cost_scale_arg(spec):
+    """``--rl_cost_scale``: a finite float >= 0."""
+    k = _finite_float(spec)
+    if k is None or not k >= 0.0:
+        raise argparse.ArgumentTypeError('--rl_cost_scale must be finite and >= 0, got %r' % spec)
+    return k
+
+
 def build_parser():
     p = argparse.ArgumentParser(
         description='MI355X-native consensus/self-critical video captioning trainer')
@@ -206,6 +233,22 @@ def build_parser():
              'the fused Adam pass, and validate / select / save the best checkpoint with it '
              '(the _last.pth sidecar keeps the live weights, the EMA in its optimizer state).  '
              '0 (default): off')
+    add('--rl_objective', type=str, default='reinforce', choices=list(RL_OBJECTIVES),
+        help='RL objective: reinforce (default) = REINFORCE with the baseline of the recipe '
+             '(SCST / CST); risk, softmax_margin, multi_margin = sequence-level structured losses '
+             'over each video\'s --train_seq_per_img sampled captions (expected risk; '
+             'softmax-margin and multi-margin against the best-scored sample), on their '
+             'length-normalised log-probabilities and the scores of the reward scorer '
+             '(models/criteria.py GroupCriterion; one launch on the fused path, '
+             'ops/scst_loss.py group_loss).  No greedy decode; --scb_captions / --scb_baseline '
+             'are ignored.  Needs --use_rl 1 --use_mixer 1 --expand_feat 1 and at least 2 '
+             'captions per video')
+    add('--rl_alpha', type=rl_alpha_arg, default=1.0, metavar='A',
+        help='--rl_objective risk / *_margin: scale of the length-normalised sequence scores '
+             '(finite, > 0)')
+    add('--rl_cost_scale', type=rl_cost_scale_arg, default=1.0, metavar='K',
+        help='--rl_objective risk / *_margin: cost of a caption = K * (best score of the '
+             'video\'s samples - its score) (finite, >= 0)')
     add('--profile_phases', type=int, default=0, help='log per-phase HIP-event timings')
     return p
 

@@ -5,7 +5,12 @@ REINFORCE loss in one launch forward and one backward (reference
 ``train.py:182-194, 223-246`` for the logged means).  Same arithmetic as
 :func:`~cst_captioning_amd.reward.rewards.scst_from_scores` /
 :func:`~cst_captioning_amd.reward.rewards.cst_from_scores` followed by
-:class:`~cst_captioning_amd.models.criteria.RewardCriterion`, fp32."""
+:class:`~cst_captioning_amd.models.criteria.RewardCriterion`, fp32.
+
+:func:`group_loss` (``--rl_objective``): the group objectives over each
+video's rollout rows -- expected risk, softmax-margin, multi-margin -- through
+the same two entry points, the arithmetic of
+:class:`~cst_captioning_amd.models.criteria.GroupCriterion`."""
 import torch
 
 from .. import _ext
@@ -81,4 +86,40 @@ def cst_loss(seq, logprobs, scores, bcmrscores, scb_captions, scb_baseline):
     bref = bcmrscores if (scb_captions > 0 and scb_baseline == 1) else None
     loss, reward, out = _SCSTLossFn.apply(seq.contiguous(), logprobs, scores, bref,
                                           (int(S), min(int(scb_captions), int(S))))
+    return loss, reward, out[1], out[2]
+
+
+_GROUP_KIND = {'risk': 1, 'softmax_margin': 2, 'multi_margin': 3}  # (csrc/launchers.h)
+
+
+class _GroupLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, seq, lp, scores, S, kind, alpha, cost_scale):
+        loss, out, reward, w = _ext.ops().cst_loss_forward(
+            seq, lp.detach().float().contiguous(), scores.detach().float().contiguous().reshape(-1),
+            torch.empty(0, device=lp.device), S, 0, kind, alpha, cost_scale)
+        ctx.save_for_backward(seq, w, out)
+        ctx.mark_non_differentiable(reward, out)
+        return loss, reward, out
+
+    @staticmethod
+    def backward(ctx, dloss, _dr, _do):
+        seq, w, out = ctx.saved_tensors
+        dlp = _ext.ops().scst_loss_backward(seq, w, out, dloss.float().reshape(1).contiguous(), w)
+        return None, dlp, None, None, None, None, None
+
+
+def group_loss(seq, logprobs, scores, objective, alpha=1.0, cost_scale=1.0):
+    """(loss, reward (R,), m, b) of a group objective (``--rl_objective``:
+    risk, softmax_margin, multi_margin) over each video's rollout rows:
+    ``scores`` (B, S) of the rows, 2 <= S <= 64.  One launch forward, one
+    backward; the arithmetic of
+    :class:`~cst_captioning_amd.models.criteria.GroupCriterion`, fp32."""
+    from ..models.criteria import check_group_objective
+    objective, alpha, cost_scale = check_group_objective(objective, alpha, cost_scale)
+    if scores.dim() != 2:
+        raise ValueError('group_loss: scores (B, S)')
+    loss, reward, out = _GroupLossFn.apply(seq.contiguous(), logprobs, scores,
+                                           int(scores.size(1)), _GROUP_KIND[objective], alpha,
+                                           cost_scale)
     return loss, reward, out[1], out[2]

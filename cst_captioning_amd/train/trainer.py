@@ -8,7 +8,10 @@ Behaviour of ``/root/reference/train.py:45-418``:
   * RL (``--use_rl 1`` from epoch ``use_rl_after``; 0 = the resume epoch):
       - SCST (``use_cst 0``): greedy decode baseline (``train.py:175-180``),
       - CST (``use_cst 1``): consensus baseline from GT or sample scores,
-      - WXE (``use_cst 1, use_mixer 0``): precomputed GT scores as weights;
+      - WXE (``use_cst 1, use_mixer 0``): precomputed GT scores as weights,
+      - (not in the reference) ``--rl_objective risk / softmax_margin /
+        multi_margin``: a structured loss over each video's samples and their
+        scores in place of REINFORCE, no baseline decode;
   * LR step decay on epoch change; validation + best-model checkpoint from
     ``save_checkpoint_from``; stop at ``max_epochs`` or after
     ``max_patience`` epochs without improvement.
@@ -31,7 +34,7 @@ import time
 import numpy as np
 import torch
 
-from ..models import CrossEntropyCriterion, RewardCriterion
+from ..models import CrossEntropyCriterion, GroupCriterion, RewardCriterion
 from ..ops.adam import FlatAdam
 from ..ops.cider_d import CiderDScorer, GenericScorer
 from ..parallel import FlatGradBucket
@@ -144,6 +147,7 @@ class Trainer:
         self.device = self.ctx.device
         self.xe_criterion = CrossEntropyCriterion()
         self.rl_criterion = RewardCriterion()
+        self.group_criterion = self._build_group_criterion()  # (--rl_objective)
         self.ctx.broadcast_module(model)
         # bucket order = the order the fused backward finalises gradients:
         # vocab head (under the reverse loop), embedding (post-loop tail), rest
@@ -250,6 +254,36 @@ class Trainer:
         self._ev_inputs = None
 
     # ------------------------------------------------------------------ RL ---
+    def _build_group_criterion(self):
+        """--rl_objective risk / softmax_margin / multi_margin: the criterion
+        of the group objective (None with reinforce); raises ``ValueError``
+        for a recipe the objective is not defined on, so that set-up fails and
+        not the first RL step."""
+        opt = self.opt
+        objective = getattr(opt, 'rl_objective', 'reinforce')
+        if objective == 'reinforce':
+            return None
+        crit = GroupCriterion(objective, getattr(opt, 'rl_alpha', 1.0),
+                              getattr(opt, 'rl_cost_scale', 1.0))
+        if opt.use_rl != 1:
+            raise ValueError('--rl_objective %s is an RL objective: it needs --use_rl 1'
+                             % objective)
+        if opt.use_mixer != 1:
+            raise ValueError('--rl_objective %s scores the sampled captions: it needs '
+                             '--use_mixer 1 (WXE rewards the GT rows, not samples)' % objective)
+        if opt.expand_feat != 1:
+            raise ValueError('--rl_objective %s compares the samples of one video: it needs '
+                             '--expand_feat 1' % objective)
+        S = (self.train_loader.get_seq_per_img() if self.train_loader is not None
+             else opt.train_seq_per_img)
+        if S < 2:
+            raise ValueError('--rl_objective %s needs at least 2 sampled captions per video '
+                             '(--train_seq_per_img %d)' % (objective, S))
+        logger.info('RL objective: %s (alpha %g, cost scale %g) over each video\'s %d samples; '
+                    'no greedy decode, --scb_captions / --scb_baseline are ignored',
+                    objective, crit.alpha, crit.cost_scale, S)
+        return crit
+
     def _ensure_scorer(self):
         if self.scorer is None:
             self.scorer = build_scorer(self.opt, self.train_loader.ds, self.device)
@@ -305,7 +339,10 @@ class Trainer:
         scorer = self._ensure_scorer()
         vid_rows = data['video_index'].repeat_interleave(S)
         side = None
-        if opt.use_cst == 0 and self.device.type == 'cuda':
+        # --rl_objective risk / *_margin: a loss over each video's samples and
+        # their scores alone -- no greedy decode, no side stream, no baseline
+        group = self.group_criterion
+        if opt.use_cst == 0 and group is None and self.device.type == 'cuda':
             # The greedy baseline only depends on the inputs and the current
             # weights: decode + score it on a second HIP stream, concurrently
             # with the rollout on the main stream.
@@ -330,7 +367,8 @@ class Trainer:
             inputs_ready.record(main)
         # fused engine: reward, mask and REINFORCE loss in one launch
         # (ops/scst_loss.py), the greedy scores per video
-        fused = self.engine is not None and opt.use_cst == 0 and self.device.type == 'cuda'
+        fused = (self.engine is not None and opt.use_cst == 0 and group is None
+                 and self.device.type == 'cuda')
 
         def enqueue_greedy():
             inputs_ready.record(main)  # (everything main enqueued so far)
@@ -362,6 +400,20 @@ class Trainer:
             self.engine.launch_x()
         stamps.base(None)
         self.timer.mark('rollout')
+        if group is not None:
+            scores = scorer.score(model_res, vid_rows).float().view(-1, S)
+            stamps.mark('sample_scores')
+            if self.engine is not None and self.device.type == 'cuda' and S <= 64:
+                # fused: sequence scores, costs, the objective and the logged
+                # means in one launch (csrc/kernels/loss.hip, group objectives)
+                from ..ops.scst_loss import group_loss
+                loss, reward, m_score, b_score = group_loss(
+                    model_res, logprobs, scores, group.objective, group.alpha, group.cost_scale)
+                stamps.mark('loss')
+            else:
+                loss, reward, m_score, b_score = group(model_res, logprobs, scores)
+            self.timer.mark('reward')
+            return loss, {'reward': reward, 'm': m_score, 'b': b_score, 'seq': model_res}
         if opt.use_cst == 0:
             sample_scores = scorer.score(model_res, vid_rows)
             stamps.mark('sample_scores')

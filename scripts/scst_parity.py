@@ -12,6 +12,9 @@ CSTCAP_PARITY_TASK=template uses the learnable template captions
 modalities, V = 10,509, 64 videos x 20 captions per step) instead of the
 small default (H = 256, V = 2,000, 32 videos).  Every log line also carries
 the optimizer's NaN-guard skip count and the exp-store rows recomputed.
+CSTCAP_PARITY_OBJECTIVE=risk (or softmax_margin, multi_margin) runs the RL
+phase under that --rl_objective instead of SCST; the log's b is then the
+objective's logged baseline.
 """
 import json
 import os
@@ -47,7 +50,8 @@ tr, va, _ = make_splits('msrvtt', vocab_size=V_, feat_dims=FD_, train_videos=NV_
 opt = default_opts(batch_size=B_, train_seq_per_img=20, rnn_size=H_, input_encoding_size=H_,
                    learning_rate=2e-3, max_epochs=10 ** 9, print_log_interval=0, impl=impl,
                    precision=precision, loglevel='WARNING', use_rl=1, use_rl_after=10 ** 6,
-                   use_cst=0, use_mixer=1, mixer_from=1, use_eos=1, drop_prob_lm=0.5)
+                   use_cst=0, use_mixer=1, mixer_from=1, use_eos=1, drop_prob_lm=0.5,
+                   rl_objective=os.environ.get('CSTCAP_PARITY_OBJECTIVE', 'reinforce'))
 opt.vocab = {i: w for i, w in enumerate(tr.vocab)}
 opt.vocab_size, opt.seq_length, opt.feat_dims = tr.vocab_size, tr.seq_length, tr.feat_dims
 loader = CaptionLoader(tr, B_, 20, 'train', dev, seed=0)
@@ -112,4 +116,4 @@ for g in t.optimizer.param_groups:
 for it in range(rl_steps):
     out = t.train_step(loader.get_batch(), 0)
     if it % 25 == 0 or it == rl_steps - 1:
-        log('scst', it, out)
+        log('scst' if opt.rl_objective == 'reinforce' else opt.rl_objective, it, out)
