@@ -419,4 +419,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wgrad_tn", &cst::wgrad_tn);
   m.def("wgrad_tn_colsum", &cst::wgrad_tn_colsum);
   m.def("wgrad_tn_rows", &cst::wgrad_tn_rows);
+  // the backward's gradient-assembly kernels one by one (tests); empty tensors = not given
+  m.def("vgrad_fold", &cst::vgrad_fold, py::arg("E"), py::arg("lse"), py::arg("y_sel"),
+        py::arg("dg_sel"), py::arg("labels"), py::arg("dg_xe"), py::arg("V"),
+        py::arg("zero_off"), py::arg("hd"), py::arg("wlog"), py::arg("blog"),
+        py::arg("fix_total"), py::arg("forward_x"), py::arg("X"));
+  m.def("vgrad_rows", &cst::vgrad_rows, py::arg("alpha"), py::arg("hd"), py::arg("ldhs"),
+        py::arg("dhd"));
+  m.def("vgrad_colsum", &cst::vgrad_colsum);
+  m.def("video_gate_grad", &cst::video_gate_grad);
 }

@@ -479,11 +479,14 @@ std::vector<at::Tensor> token_sort(at::Tensor toks, int64_t V) {
   return {stok, srow};
 }
 
-// per-token row sums for tests: x (N, C) bf16, toks (N) int64 -> S (V, C) bf16
+// per-token row sums for tests: x (N, C) bf16 (rows x.stride(0) apart: a
+// column slice of a wider tensor will do), toks (N) int64 -> S (V, C) bf16
 at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V) {
-  check_cuda(x, "x");
   check_cuda(toks, "toks");
-  TORCH_CHECK(x.scalar_type() == at::kBFloat16 && x.dim() == 2 && x.stride(1) == 1, "x: (N, C) bf16");
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.dim() == 2 &&
+                  x.stride(1) == 1 && x.stride(0) >= x.size(1) &&
+                  reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+              "x: (N, C) bf16, unit column stride, 16-byte aligned");
   TORCH_CHECK(toks.scalar_type() == at::kLong && toks.numel() == x.size(0), "toks: (N) int64");
   const int64_t N = toks.numel(), C = x.size(1);
   auto i32 = at::TensorOptions().dtype(at::kInt).device(toks.device());
@@ -499,6 +502,162 @@ at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V) {
                          (int)V, reinterpret_cast<uint16_t*>(S.data_ptr()), S64.data_ptr<double>(),
                          st);
   return S;
+}
+
+// vgrad_onehot (+ vgrad_fix when hd is given) alone, for tests: E (n, R, ldl)
+// bf16 folded in place; lse (n, R); y_sel / dg_sel (R, T_sel) or both empty;
+// labels (R, >= n + 1) int64 / dg_xe (R, >= n) with their own row strides, or
+// both empty (y_xe = labels + 1 as in the backward's onehot_pass).  hd (n R, H)
+// bf16 + wlog (V, H) bf16 + blog (V) + fix_total (int32 word) switch the range
+// guard on.  forward_x: the one-hot weights / tokens are written out too, and
+// with the guard the listed rows of X (n R, H) fp32 (empty: zeros) recomputed.
+// Returns {alpha (n R), fix (1 + n R int32)[, oh_a, oh_ys, oh_b, oh_yx, X]}.
+std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_sel,
+                                   at::Tensor dg_sel, at::Tensor labels, at::Tensor dg_xe,
+                                   int64_t V, int64_t zero_off, at::Tensor hd, at::Tensor wlog,
+                                   at::Tensor blog, at::Tensor fix_total, bool forward_x,
+                                   at::Tensor X) {
+  check_cuda(E, "E");
+  check_cuda(lse, "lse");
+  TORCH_CHECK(E.scalar_type() == at::kBFloat16 && E.dim() == 3, "vgrad_fold: E (n, R, ldl) bf16");
+  const int64_t n = E.size(0), R = E.size(1), ldl = E.size(2), NR = n * R;
+  TORCH_CHECK(NR > 0 && V > 0 && V <= ldl && lse.scalar_type() == at::kFloat && lse.dim() == 2 &&
+                  lse.size(0) == n && lse.size(1) == R,
+              "vgrad_fold: V <= ldl, lse (n, R) fp32");
+  auto in_vocab = [&](const at::Tensor& t) { return t.max().item<int64_t>() < V; };
+  const bool has_sel = dg_sel.defined() && dg_sel.numel() > 0;
+  const bool has_xe = dg_xe.defined() && dg_xe.numel() > 0;
+  int64_t T_sel = 0;
+  if (has_sel) {
+    check_cuda(y_sel, "y_sel");
+    check_cuda(dg_sel, "dg_sel");
+    T_sel = y_sel.dim() == 2 ? y_sel.size(1) : 0;
+    TORCH_CHECK(y_sel.scalar_type() == at::kLong && dg_sel.scalar_type() == at::kFloat &&
+                    y_sel.dim() == 2 && y_sel.size(0) == R && T_sel > 0 &&
+                    dg_sel.sizes() == y_sel.sizes() && in_vocab(y_sel),
+                "vgrad_fold: y_sel int64 / dg_sel fp32 (R, T_sel), tokens < V");
+  }
+  if (has_xe) {
+    TORCH_CHECK(labels.is_cuda() && dg_xe.is_cuda() && labels.scalar_type() == at::kLong &&
+                    dg_xe.scalar_type() == at::kFloat && labels.dim() == 2 && dg_xe.dim() == 2 &&
+                    labels.stride(1) == 1 && dg_xe.stride(1) == 1 && labels.size(0) == R &&
+                    dg_xe.size(0) == R && labels.size(1) >= n + 1 && dg_xe.size(1) >= n &&
+                    labels.stride(0) >= labels.size(1) && dg_xe.stride(0) >= dg_xe.size(1) &&
+                    in_vocab(labels),
+                "vgrad_fold: labels int64 (R, >= n + 1) / dg_xe fp32 (R, >= n), tokens < V");
+  }
+  const bool guard = hd.defined() && hd.numel() > 0;
+  int64_t H = 0;
+  if (guard) {
+    check_cuda(hd, "hd");
+    check_cuda(wlog, "wlog");
+    check_cuda(blog, "blog");
+    check_cuda(fix_total, "fix_total");
+    H = hd.dim() == 2 ? hd.size(1) : 0;
+    TORCH_CHECK(hd.scalar_type() == at::kBFloat16 && hd.dim() == 2 && hd.size(0) == NR &&
+                    wlog.scalar_type() == at::kBFloat16 && wlog.dim() == 2 && wlog.size(0) == V &&
+                    wlog.size(1) == H && blog.scalar_type() == at::kFloat && blog.numel() == V &&
+                    fix_total.scalar_type() == at::kInt && fix_total.numel() >= 1,
+                "vgrad_fold: hd (n R, H) / wlog (V, H) bf16, blog (V) fp32, fix_total int32");
+  }
+  auto dev = E.device();
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+  auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
+  at::Tensor alpha = at::empty({NR}, f32), fix = at::zeros({1 + NR}, i32);
+  at::Tensor oh_a, oh_ys, oh_b, oh_yx;
+  if (forward_x) {
+    oh_a = at::empty({NR}, f32), oh_b = at::empty({NR}, f32);
+    oh_ys = at::empty({NR}, i32), oh_yx = at::empty({NR}, i32);
+    if (guard) {
+      if (X.defined() && X.numel() > 0) {
+        check_cuda(X, "X");
+        TORCH_CHECK(X.scalar_type() == at::kFloat && X.dim() == 2 && X.size(0) == NR &&
+                        X.size(1) == H, "vgrad_fold: X (n R, H) fp32");
+      } else {
+        X = at::zeros({NR, H}, f32);
+      }
+    }
+  }
+  const bool have_x = forward_x && guard;
+  VGradRows va{(int)R, (int)n, (int)T_sel, (int)H, (int)V, lse.data_ptr<float>(),
+               has_sel ? y_sel.data_ptr<int64_t>() : nullptr,
+               has_sel ? dg_sel.data_ptr<float>() : nullptr,
+               has_xe ? labels.data_ptr<int64_t>() + 1 : nullptr, has_xe ? labels.stride(0) : 0,
+               has_xe ? dg_xe.data_ptr<float>() : nullptr, has_xe ? dg_xe.stride(0) : 0,
+               guard ? fix.data_ptr<int>() : nullptr, ptr_or_null<float>(oh_a),
+               ptr_or_null<int>(oh_ys), ptr_or_null<float>(oh_b), ptr_or_null<int>(oh_yx),
+               have_x ? X.data_ptr<float>() : nullptr, zero_off ? 1 : 0};
+  hipStream_t st = cur_stream();
+  launch_vgrad_onehot(va, reinterpret_cast<uint16_t*>(E.data_ptr()), ldl, alpha.data_ptr<float>(),
+                      st);
+  if (guard)
+    launch_vgrad_fix(va, reinterpret_cast<const uint16_t*>(hd.data_ptr()),
+                     reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(),
+                     reinterpret_cast<uint16_t*>(E.data_ptr()), ldl, alpha.data_ptr<float>(),
+                     fix_total.data_ptr<int>(), st);
+  std::vector<at::Tensor> out{alpha, fix};
+  if (forward_x) {
+    out.insert(out.end(), {oh_a, oh_ys, oh_b, oh_yx});
+    if (guard) out.push_back(X);
+  }
+  return out;
+}
+
+// scaled rows for tests: hs (NR, ldhs) bf16 = alpha . hd, the augmented
+// columns as the kernel writes them; dhd (NR, H) fp32 or empty, scaled in place
+at::Tensor vgrad_rows(at::Tensor alpha, at::Tensor hd, int64_t ldhs, at::Tensor dhd) {
+  check_cuda(alpha, "alpha");
+  check_cuda(hd, "hd");
+  TORCH_CHECK(hd.scalar_type() == at::kBFloat16 && hd.dim() == 2 &&
+                  alpha.scalar_type() == at::kFloat && alpha.numel() == hd.size(0),
+              "vgrad_rows: hd (NR, H) bf16, alpha (NR) fp32");
+  const int64_t NR = hd.size(0), H = hd.size(1);
+  const bool has_dhd = dhd.defined() && dhd.numel() > 0;
+  if (has_dhd) {
+    check_cuda(dhd, "dhd");
+    TORCH_CHECK(dhd.scalar_type() == at::kFloat && dhd.dim() == 2 && dhd.size(0) == NR &&
+                    dhd.size(1) == H, "vgrad_rows: dhd (NR, H) fp32");
+  }
+  TORCH_CHECK(NR > 0 && ldhs >= H, "vgrad_rows: ldhs >= H");
+  at::Tensor hs = at::empty({NR, ldhs}, hd.options());
+  launch_vgrad_rows(alpha.data_ptr<float>(), NR, (int)H,
+                    reinterpret_cast<const uint16_t*>(hd.data_ptr()),
+                    has_dhd ? dhd.data_ptr<float>() : nullptr,
+                    reinterpret_cast<uint16_t*>(hs.data_ptr()), cur_stream(), (int)ldhs);
+  return hs;
+}
+
+// bias-gradient column sums for tests: E (NR, ldl) bf16, alpha (NR) -> db (V) fp32
+at::Tensor vgrad_colsum(at::Tensor E, at::Tensor alpha, int64_t V) {
+  check_cuda(E, "E");
+  check_cuda(alpha, "alpha");
+  TORCH_CHECK(E.scalar_type() == at::kBFloat16 && E.dim() == 2 &&
+                  alpha.scalar_type() == at::kFloat && alpha.numel() == E.size(0) &&
+                  E.size(0) > 0 && V > 0 && V <= E.size(1),
+              "vgrad_colsum: E (NR, ldl >= V) bf16, alpha (NR) fp32");
+  const int64_t NR = E.size(0), ldl = E.size(1);
+  auto f32 = at::TensorOptions().dtype(at::kFloat).device(E.device());
+  at::Tensor part = at::empty({vgrad_colsum_blocks(NR), V}, f32), db = at::empty({V}, f32);
+  launch_vgrad_colsum(reinterpret_cast<const uint16_t*>(E.data_ptr()), ldl, (int)V, NR,
+                      alpha.data_ptr<float>(), part.data_ptr<float>(), db.data_ptr<float>(),
+                      cur_stream());
+  return db;
+}
+
+// video-gate gradient for tests: dG (n, R, >= G4) bf16 (rows ld apart, steps
+// R ld apart) -> (R / vdiv, G4) fp32 sums over the steps and each video's rows
+at::Tensor video_gate_grad(at::Tensor dG, int64_t vdiv, int64_t G4) {
+  TORCH_CHECK(dG.is_cuda() && dG.scalar_type() == at::kBFloat16 && dG.dim() == 3 &&
+                  dG.numel() > 0 && dG.stride(2) == 1 && dG.size(2) >= G4 &&
+                  dG.stride(1) >= dG.size(2) && dG.stride(0) == dG.size(1) * dG.stride(1) &&
+                  reinterpret_cast<uintptr_t>(dG.data_ptr()) % 16 == 0,
+              "video_gate_grad: dG (n, R, >= G4) bf16, unit column stride, 16-byte rows");
+  const int64_t n = dG.size(0), R = dG.size(1);
+  TORCH_CHECK(vdiv > 0 && R % vdiv == 0, "video_gate_grad: R a multiple of vdiv");
+  at::Tensor out = at::empty({R / vdiv, G4}, dG.options().dtype(at::kFloat));
+  launch_video_gate_grad(reinterpret_cast<const uint16_t*>(dG.data_ptr()), dG.stride(1), (int)n,
+                         (int)R, (int)vdiv, (int)G4, out.data_ptr<float>(), cur_stream());
+  return out;
 }
 
 }  // namespace cst

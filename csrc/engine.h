@@ -143,6 +143,14 @@ std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor
                                          double ss_prob);
 std::vector<at::Tensor> token_sort(at::Tensor toks, int64_t V);
 at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V);
+std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_sel,
+                                   at::Tensor dg_sel, at::Tensor labels, at::Tensor dg_xe,
+                                   int64_t V, int64_t zero_off, at::Tensor hd, at::Tensor wlog,
+                                   at::Tensor blog, at::Tensor fix_total, bool forward_x,
+                                   at::Tensor X);
+at::Tensor vgrad_rows(at::Tensor alpha, at::Tensor hd, int64_t ldhs, at::Tensor dhd);
+at::Tensor vgrad_colsum(at::Tensor E, at::Tensor alpha, int64_t V);
+at::Tensor video_gate_grad(at::Tensor dG, int64_t vdiv, int64_t G4);
 at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K);
 void wgrad_tn_rows(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K, at::Tensor out,
                    at::Tensor rmap);
