@@ -362,7 +362,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("token_sort", &cst::token_sort);
   m.def("token_group_sum", &cst::token_group_sum);
   m.def("vocab_select", &cst::vocab_select);
-  m.def("decode_step_test", &cst::decode_step_test);
+  m.def("decode_step_test", &cst::decode_step_test, py::arg("hd"), py::arg("h"), py::arg("wlog"),
+        py::arg("blog"), py::arg("whh"), py::arg("vgate"), py::arg("vdiv"), py::arg("tgt"),
+        py::arg("eoff"), py::arg("save"), py::arg("mode"), py::arg("step"), py::arg("rng"),
+        py::arg("ptab"), py::arg("c_prev"), py::arg("drop_p"), py::arg("cell"), py::arg("eos"),
+        py::arg("unfinished"), py::arg("ss_prob"), py::arg("want_xe") = true);
   m.def("gemm_bf16_tuned", &cst::gemm_bf16_tuned, py::arg("out"), py::arg("a"), py::arg("ta"),
         py::arg("b"), py::arg("tb"), py::arg("n_cand") = 24);
   m.def("gemm_bf16_tuned_batched", &cst::gemm_bf16_tuned_batched, py::arg("out"), py::arg("a"),

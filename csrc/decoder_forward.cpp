@@ -366,6 +366,9 @@ struct Rollout {
       const bool exp_t = save && store_exp && t > 0;  // step 0: fp16, converted below
       const int vflags = do_sample | ((choose && mode == SEL_GREEDY_H) ? 2 : 0) | (exp_t ? 16 : 0);
       const TokRows tgt = (have_labels && t + 1 < L) ? LABR.col(t + 1) : TokRows();
+      // the launch looks the target token's logit up only where this step's
+      // combine reads it (the combine keeps the token itself)
+      const TokRows tgt_x = vocab_step_reads_target(want_xe, choose, mode) ? tgt : TokRows();
       // attention: the same launch also projects q_{t+1} = h_t W_q^T (extra
       // W_q tiles of the recurrent GEMM, no vgate add); the attention kernel then
       // adds each row's video term into pre before the combine's cell epilogue
@@ -386,7 +389,7 @@ struct Rollout {
       const int n_vt = launch_vocab_lstm_fwd(
           vin, (int)H, (int)R, (int)H, W, blog.data_ptr<float>(), (int)V,
           save ? reinterpret_cast<uint16_t*>(logits16[t].data_ptr()) : nullptr, ldl, part.data_ptr(),
-          tgt, L, vflags, inv_temp, RNG, (int)t, h_buf(0, t), WHH, has_att ? nullptr : VG, VDIV,
+          tgt_x, L, vflags, inv_temp, RNG, (int)t, h_buf(0, t), WHH, has_att ? nullptr : VG, VDIV,
           next ? reinterpret_cast<float*>(pre.data_ptr()) : nullptr, st, q_tiles ? (int)A : 0,
           q_tiles && next ? q_next.data_ptr<float>() : nullptr,
           exp_t ? lse[t - 1].data_ptr<float>() : nullptr, att_mfma && next ? &am : nullptr,

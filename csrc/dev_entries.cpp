@@ -373,14 +373,16 @@ std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor 
 // end-of-sequence rules; 1 / 2 the all-rows-ended counter with a live / dead
 // previous step; unfinished (R) uint8 nullable: the per-row mask, updated in
 // place.  Returns {lse, tok, g_sel, g_xe, saved rows (R, ldl), pre (R, 4H),
-// n_parts, h, c, h_drop, gates, counts}.
+// n_parts, h, c, h_drop, gates, counts, part}.  want_xe: g_xe is asked for
+// (given tgt); the launch gets the target under the executor's rule
+// (vocab_step_reads_target), the combine always.
 std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor wlog,
                                          at::Tensor blog, at::Tensor whh, at::Tensor vgate,
                                          int64_t vdiv, at::Tensor tgt, at::Tensor eoff,
                                          int64_t save, int64_t mode, int64_t step, at::Tensor rng,
                                          at::Tensor ptab, at::Tensor c_prev, double drop_p,
                                          int64_t cell, int64_t eos, at::Tensor unfinished,
-                                         double ss_prob) {
+                                         double ss_prob, bool want_xe) {
   check_cuda(hd, "hd");
   check_cuda(wlog, "wlog");
   const int64_t R = hd.size(0), H = hd.size(1), V = wlog.size(0);
@@ -441,11 +443,13 @@ std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor
   const int flags = (mode == SEL_SAMPLE_H || mode == SEL_SS_H ? 1 : 0) |
                     (mode == SEL_GREEDY_H ? 2 : 0) | (save == 2 ? 16 : 0);
   const int64_t* TG = has_tgt ? tgt.data_ptr<int64_t>() : nullptr;
+  const bool xe = has_tgt && want_xe;
+  const int64_t* TGX = vocab_step_reads_target(xe, true, (int)mode) ? TG : nullptr;
   uint8_t* UNF = has_unf ? unfinished.data_ptr<uint8_t>() : nullptr;
   const int n = launch_vocab_lstm_fwd(
       reinterpret_cast<const uint16_t*>(hd.data_ptr()), (int)H, (int)R, (int)H,
       reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(), (int)V,
-      save ? reinterpret_cast<uint16_t*>(saved.data_ptr()) : nullptr, ldl, part.data_ptr(), TG, 1,
+      save ? reinterpret_cast<uint16_t*>(saved.data_ptr()) : nullptr, ldl, part.data_ptr(), TGX, 1,
       flags, 1.f, rng_ptr(rng), (int)step,
       lstm ? reinterpret_cast<const uint16_t*>(h.data_ptr()) : nullptr,
       lstm ? reinterpret_cast<const uint16_t*>(whh.data_ptr()) : nullptr,
@@ -460,11 +464,11 @@ std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor
                     reinterpret_cast<uint16_t*>(gates.data_ptr()), (int)H, (float)drop_p,
                     (int)step + 1, (int)cell, nullptr, 0};
   launch_vocab_combine(part.data_ptr(), n, (int)R, lse.data_ptr<float>(), tok.data_ptr<int64_t>(),
-                       1, gsel.data_ptr<float>(), 1, has_tgt ? gxe.data_ptr<float>() : nullptr, 1,
+                       1, gsel.data_ptr<float>(), 1, xe ? gxe.data_ptr<float>() : nullptr, 1,
                        TG, 1, (int)mode, (float)ss_prob, rng_ptr(rng), (int)step, CNT, 2, UNF, st,
                        do_cell ? &cl : nullptr);
   return {lse, tok, gsel, gxe, saved, pre, at::full({1}, n, at::TensorOptions().dtype(at::kLong)),
-          h_out, c_out, hdrop, gates, counts};
+          h_out, c_out, hdrop, gates, counts, part};
 }
 
 // the counting sort itself, for tests: returns {stok, srow} (int32)

@@ -140,7 +140,7 @@ std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor
                                          int64_t save, int64_t mode, int64_t step, at::Tensor rng,
                                          at::Tensor ptab, at::Tensor c_prev, double drop_p,
                                          int64_t cell, int64_t eos, at::Tensor unfinished,
-                                         double ss_prob);
+                                         double ss_prob, bool want_xe = true);
 std::vector<at::Tensor> token_sort(at::Tensor toks, int64_t V);
 at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V);
 std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_sel,

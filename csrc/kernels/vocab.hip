@@ -21,7 +21,8 @@
 //     driven by counter hashes of (seed, step, row, tile), so no per-element
 //     random numbers (the seed is read from device memory, so a replayed
 //     HIP graph draws fresh samples);
-//     greedy argmax, and the logit of the row's target token.
+//     greedy argmax, and the logit of the row's target token (only in the
+//     launches whose combine reads it: launchers.h vocab_step_reads_target).
 // vocab_combine_kernel (one wavefront per row)
 //   * merges the tile partials: LSE, sampled / greedy / target token and
 //     their log-probs; applies the step's token-selection mode (teacher
@@ -51,7 +52,11 @@ namespace cst {
 // waves) are merged, through 16 KB of LDS, once per block.
 //
 // Sampling stays exact: each group draws inside its own 32 weights by inverse
-// CDF and enters an exponential race with key m/temp + log(mass) - log(E)
+// CDF -- the running sum never decreases, so the drawn position is the COUNT of
+// positions whose running sum lies below the threshold (one compare and one
+// add-with-carry each), and its logit comes out of a 5-level select tree
+// (pick32); no candidate / logit pair is carried through the 32 positions --
+// and enters an exponential race with key m/temp + log(mass) - log(E)
 // (E ~ Exp(1)); the race continues across the 4 groups here and across vocab
 // tiles in vocab_combine_kernel, and the union of independent races is the
 // race over all of V.
@@ -77,6 +82,40 @@ struct GroupStat {  // 32 bytes, one per (lane group, row) in LDS (exp_stage_off
       const float *__restrict__ eoff
 #define VOCAB_TR_ARGS \
   hd, ldh, R, H, W, bias, V, logits16, ldl, part, tgt, tgt_stride, flags, inv_temp, rng, step, eoff
+
+// x[n] of the lane's 32 logits, n = 16 i + k in [0, 32): a 5-level select tree
+// (5 bit tests + 31 selects) instead of a compare and a select per position
+// (operands by value: a conditional on two elements of one array is an lvalue,
+// read through a selected address, which puts the array in scratch memory)
+__device__ __forceinline__ float sel32(bool c, float hi, float lo) { return c ? hi : lo; }
+__device__ __forceinline__ float pick32(const float (&x)[2][16], int n) {
+  const bool b0 = n & 1, b1 = n & 2, b2 = n & 4, b3 = n & 8, b4 = n & 16;
+  float a[16], b[8], c[4];
+#pragma unroll
+  for (int p = 0; p < 8; ++p) {
+    a[p] = sel32(b0, x[0][2 * p + 1], x[0][2 * p]);
+    a[8 + p] = sel32(b0, x[1][2 * p + 1], x[1][2 * p]);
+  }
+#pragma unroll
+  for (int p = 0; p < 8; ++p) b[p] = sel32(b1, a[2 * p + 1], a[2 * p]);
+#pragma unroll
+  for (int p = 0; p < 4; ++p) c[p] = sel32(b2, b[2 * p + 1], b[2 * p]);
+  return sel32(b4, sel32(b3, c[3], c[2]), sel32(b3, c[1], c[0]));
+}
+// a[k] = fma(x[k], sc, off) as packed pairs (element-wise, so IEEE-identical
+// to 16 fmaf)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void exp2_args(float (&a)[16], const float (&x)[16], float sc, float off) {
+#pragma unroll
+  for (int k = 0; k < 16; k += 2) {
+    const f32x2 r = __builtin_elementwise_fma(f32x2{x[k], x[k + 1]}, f32x2{sc, sc}, f32x2{off, off});
+    a[k] = r.x, a[k + 1] = r.y;
+  }
+}
+// vocabulary index of the lane's logit n (vb: the lane's first entry)
+__device__ __forceinline__ int lane_vocab(int vb, int n) {
+  return vb + 32 * (n >> 4) + 8 * ((n >> 2) & 3) + (n & 3);
+}
 
 // TOPK (flags VF_TOPK, beam search only): the per-tile top-K candidates
 template <int BN, int STAGES, bool TOPK = false>
@@ -232,12 +271,14 @@ __device__ __forceinline__ void vocab_tr_block(int bid, char* lds, VOCAB_TR_PARA
     float ew[TM][16];
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
+    for (int i = 0; i < TM; ++i) {
+      exp2_args(ew[i], x[i], L2E, -ml);
 #pragma unroll
       for (int k = 0; k < 16; ++k) {
-        ew[i][k] = __builtin_amdgcn_exp2f(fmaf(x[i][k], L2E, -ml));
+        ew[i][k] = __builtin_amdgcn_exp2f(ew[i][k]);
         s += ew[i][k];
       }
+    }
     if ((flags & VF_EXP) && logits16 != nullptr && r < R) {
       // E = exp(x - c) = exp(x - m) * exp(m - c): one multiply per entry on
       // the weights already in registers (bf16: fp32's exponent range, so in
@@ -266,23 +307,21 @@ __device__ __forceinline__ void vocab_tr_block(int bid, char* lds, VOCAB_TR_PARA
     st.pad = 0.f;
     st.xidx = 0x7fffffff;
     if (flags & VF_ARGMAX) {
+      // the first position that holds the maximum (the vocabulary index
+      // ascends with the position): last write wins, positions descending
+      int n = 32;
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+      for (int i = TM - 1; i >= 0; --i)
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          const int v = vb + 32 * i + 8 * (k >> 2) + (k & 3);
-          st.xidx = min(st.xidx, x[i][k] == m ? v : 0x7fffffff);
-        }
+        for (int k = 15; k >= 0; --k) n = x[i][k] == m ? 16 * i + k : n;
+      st.xidx = n < 32 ? lane_vocab(vb, n) : 0x7fffffff;
     }
     st.xt = -INFINITY;
     if (tgt.p != nullptr) {
       const int d = tg[j] - vb;
       const bool mine = d >= 0 && d < 32 * TM && (d & 4) == 0;
-      const int kk = mine ? (d >> 5) * 16 + ((d >> 3) & 3) * 4 + (d & 3) : -1;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int k = 0; k < 16; ++k) st.xt = (i * 16 + k == kk) ? x[i][k] : st.xt;
+      const float xk = pick32(x, (d >> 5) * 16 + ((d >> 3) & 3) * 4 + (d & 3));
+      st.xt = mine ? xk : -INFINITY;
     }
     st.zkey = -INFINITY;
     st.zlogit = 0.f;
@@ -293,12 +332,14 @@ __device__ __forceinline__ void vocab_tr_block(int bid, char* lds, VOCAB_TR_PARA
       if (!temp1) {
         sw = 0.f;
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+        for (int i = 0; i < TM; ++i) {
+          exp2_args(ew[i], x[i], wsc, -wl);
 #pragma unroll
           for (int k = 0; k < 16; ++k) {
-            ew[i][k] = __builtin_amdgcn_exp2f(fmaf(x[i][k], wsc, -wl));
+            ew[i][k] = __builtin_amdgcn_exp2f(ew[i][k]);
             sw += ew[i][k];
           }
+        }
       }
       const uint32_t rr = (uint32_t)min(r, R - 1);
       const uint32_t seed = rng_seed(rng, RNG_SLOT_SAMPLE);
@@ -306,26 +347,26 @@ __device__ __forceinline__ void vocab_tr_block(int bid, char* lds, VOCAB_TR_PARA
                                  (uint32_t)(vt * 4 + g) * 0xC2B2AE3Du);
       const float u = ((float)(key >> 8) + 0.5f) * (1.0f / 16777216.0f);
       const float tm = u * sw;
-      // inverse CDF in the same summation order as sw, so the last positive
-      // weight always satisfies cum >= tm
-      float cum = 0.f, cl = 0.f;
-      int cand = -1;
+      // inverse CDF in the same summation order as sw.  The weights are >= 0,
+      // so cum never decreases, and tm > 0 when sw > 0: the first position with
+      // cum >= tm is the count n of positions with cum < tm, its weight is
+      // positive, and the last positive weight closes the sum (n < 32).  A
+      // non-finite sum fails sw > 0 and leaves the row without a candidate.
+      float cum = 0.f;
+      int n = 0;
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-          const float wv = ew[i][k];
-          cum += wv;
-          const bool hit = cand < 0 && cum >= tm && wv > 0.f;
-          cand = hit ? vb + 32 * i + 8 * (k >> 2) + (k & 3) : cand;
-          cl = hit ? x[i][k] : cl;
+          cum += ew[i][k];
+          n += cum < tm ? 1 : 0;
         }
-      if (sw > 0.f && cand >= 0) {
+      if (sw > 0.f && n < 32) {
         const uint32_t key2 = mix32(key ^ 0x68E31DA4u);
         const float u2 = ((float)(key2 >> 8) + 0.5f) * (1.0f / 16777216.0f);
         st.zkey = msafe * inv_temp + __logf(sw) - __logf(-__logf(u2));
-        st.zidx = cand;
-        st.zlogit = cl;
+        st.zidx = lane_vocab(vb, n);
+        st.zlogit = pick32(x, n);
       }
     }
     gs[g * BN + row_l] = st;

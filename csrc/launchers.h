@@ -178,6 +178,15 @@ void launch_swap_refresh(float* p, float* q, int64_t n, const ShadowSegs& ss,
 
 // vocab.hip
 enum SelModeHost : int { SEL_GT_H = 0, SEL_SAMPLE_H = 1, SEL_GREEDY_H = 2, SEL_SS_H = 3 };
+// Does a decode step's combine read the target token's logit (the partials'
+// xtgt)?  From finish_row (vocab.hip): g_xe = xt - lse when g_xe is written;
+// with a token chosen, g_sel takes xt under teacher forcing and under
+// scheduled sampling (either side of its coin).  Pure sampling and greedy
+// steps read zlogit / the maximum only, so their decode launch gets no target
+// and skips the label load and the per-lane lookup.
+inline bool vocab_step_reads_target(bool want_xe, bool choose, int mode) {
+  return want_xe || (choose && (mode == SEL_GT_H || mode == SEL_SS_H));
+}
 // vocab flag of the beam search's per-tile top-K candidates (kernels/vocab_common.h
 // VF_TOPK; the beam size in bits 8..11)
 constexpr int VF_TOPK_H = 32;
