@@ -87,6 +87,8 @@ MBR_MIX?=
 # EMA of the parameters kept by the fused Adam pass; validation, the best score
 # and the best checkpoint then use the averaged weights (0 = off)
 EMA_DECAY?=0
+# label smoothing of the XE training loss, in [0, 1) (0 = plain cross-entropy)
+LABEL_SMOOTHING?=0
 # RL objective: reinforce (the recipe's REINFORCE loss), or risk /
 # softmax_margin / multi_margin over each video's sampled captions, with the
 # scale of their length-normalised log-probabilities and of the costs
@@ -192,7 +194,7 @@ TRAIN_OPT=--beam_size $(BEAM_SIZE) --max_patience $(MAX_PATIENCE) --eval_metric 
 	--loglevel $(LOGLEVEL) --model_type $(MODEL_TYPE) --use_eos $(USE_EOS) \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
 	$(if $(REWARD_MIX),--reward_mix $(REWARD_MIX)) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX)) \
-	--ema_decay $(EMA_DECAY) \
+	--ema_decay $(EMA_DECAY) --label_smoothing $(LABEL_SMOOTHING) \
 	--rl_objective $(RL_OBJECTIVE) --rl_alpha $(RL_ALPHA) --rl_cost_scale $(RL_COST_SCALE) \
 	--model_file $@ --start_from $(START_FROM) --result_file $(basename $@)_test.json \
 	2>&1 | tee $(basename $@).log

@@ -237,7 +237,17 @@ static std::vector<at::Tensor> meteor_stats_cpu(at::Tensor hyps, at::Tensor hyp_
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "cst_captioning_amd native extension: gfx950 HIP kernels + C++ decoder executor";
-  m.def("decoder_forward", &cst::decoder_forward);
+  // ls_eps / ls_wbar (label smoothing, kernels/label_smooth.hip): g_xe becomes the smoothed
+  // target log-prob; ls_wbar, fp32 (>= H + 1), receives the mean logit row and bias the
+  // backward takes back
+  m.def("decoder_forward", &cst::decoder_forward, py::arg("wx"), py::arg("emb"), py::arg("ptab"),
+        py::arg("whh"), py::arg("wlog"), py::arg("blog"), py::arg("vgate"), py::arg("vgate_div"),
+        py::arg("labels"), py::arg("bos"), py::arg("R"), py::arg("T"), py::arg("modes"),
+        py::arg("ss_prob"), py::arg("drop_p"), py::arg("temperature"), py::arg("rng"),
+        py::arg("save"), py::arg("want_xe"), py::arg("use_counts"), py::arg("use_unfinished"),
+        py::arg("att"), py::arg("cell"), py::arg("state0"), py::arg("up"), py::arg("store_exp"),
+        py::arg("xe_rows"), py::arg("lab_idx"), py::arg("ls_eps") = 0.0,
+        py::arg("ls_wbar") = py::none());
   m.def("decoder_backward", &cst::decoder_backward, py::arg("wx"), py::arg("wlog"), py::arg("emb"),
         py::arg("lse"), py::arg("logits16"), py::arg("hdrop_all"), py::arg("gates_all"),
         py::arg("c_all"), py::arg("h_all"), py::arg("seq"), py::arg("labels"), py::arg("toks"),
@@ -247,7 +257,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("blog"), py::arg("fix_total"), py::arg("vgate_div"), py::arg("xw"),
         py::arg("vg_bwd"), py::arg("vg_nf"), py::arg("vg_p"), py::arg("x_wait") = 0,
         py::arg("exp_zero_off") = false, py::arg("dw_slots") = std::vector<at::Tensor>(),
-        py::arg("vg_idx") = py::none(), py::arg("vg_C") = 1);
+        py::arg("vg_idx") = py::none(), py::arg("vg_C") = 1, py::arg("ls_eps") = 0.0,
+        py::arg("ls_wbar") = py::none());
   m.def("cider_build_tables", &cst::cider_build_tables);
   // clipped = false: coco CIDEr (no clipping, no length penalty), the validation metric
   // exclude (here and in the metric scorers below): optional (N) int64, the
@@ -427,9 +438,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vgrad_fold", &cst::vgrad_fold, py::arg("E"), py::arg("lse"), py::arg("y_sel"),
         py::arg("dg_sel"), py::arg("labels"), py::arg("dg_xe"), py::arg("V"),
         py::arg("zero_off"), py::arg("hd"), py::arg("wlog"), py::arg("blog"),
-        py::arg("fix_total"), py::arg("forward_x"), py::arg("X"));
+        py::arg("fix_total"), py::arg("forward_x"), py::arg("X"), py::arg("ls_eps") = 0.0,
+        py::arg("ls_wbar") = py::none());
   m.def("vgrad_rows", &cst::vgrad_rows, py::arg("alpha"), py::arg("hd"), py::arg("ldhs"),
         py::arg("dhd"));
-  m.def("vgrad_colsum", &cst::vgrad_colsum);
+  // ls_mode 1 / 2 / 3: label smoothing's column mean, rank-1 sums (+ the broadcast add) and
+  // smoothed log-prob kernels (dev_entries.cpp)
+  m.def("vgrad_colsum", &cst::vgrad_colsum, py::arg("E"), py::arg("alpha"), py::arg("V"),
+        py::arg("ls_mode") = 0, py::arg("ls_eps") = 0.0, py::arg("ls_dg") = py::none(),
+        py::arg("ls_dw") = py::none(), py::arg("ls_db") = py::none());
   m.def("video_gate_grad", &cst::video_gate_grad);
 }

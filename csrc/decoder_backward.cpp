@@ -89,6 +89,11 @@ struct BwdArgs {
   const std::vector<at::Tensor>& dw_slots;
   const c10::optional<at::Tensor>& vg_idx;
   const int64_t vg_C;
+  // label smoothing (kernels/label_smooth.hip): dg_xe is the gradient of the
+  // smoothed target log-prob; ls_wbar = the forward's (H + 1) column mean of
+  // the logit weights and mean bias.  0: none of it runs
+  const double ls_eps;
+  const c10::optional<at::Tensor>& ls_wbar;
 };
 
 bool nonempty(const at::Tensor& t) { return t.defined() && t.numel() > 0; }
@@ -180,6 +185,10 @@ struct Backward : BwdArgs {
   // exp-store range guard: rows whose LSE jumped by > 60 since the previous
   // step are listed and recomputed exactly (vocab_grad.hip vgrad_fix)
   const bool guard_rows;
+  // label smoothing: the uniform part of dS as three rank-1 terms -- the X
+  // shift before the loop, the broadcast add onto dW_logit / db_logit after
+  // dw_gemm (kernels/label_smooth.hip)
+  const bool ls;
   // MFMA attention path backward: dalpha partials from the step kernel's
   // epilogue (lstm.hip) + att_bwd_mfma (attention.hip); else att_bwd
   const int CPAD;
@@ -206,6 +215,7 @@ struct Backward : BwdArgs {
   at::Tensor buf, Ev, hd2, dHd;          // E (or dense dS) as bf16 / its K = V columns / Hd rows
   at::Tensor oh_a, oh_ys, oh_b, oh_yx;   // the row's one-hot weights / tokens for the loop (forward X)
   at::Tensor dWlog, dblog, alpha, hs, cs_part, fix;
+  at::Tensor ls_part, ls_gs;  // label smoothing: the rank-1 sums' partials / (H + 1) result
   at::Tensor dG_all, dc, whhT;
   at::Tensor d_emb, sort_ws, stok, srow, S_tok, S64;
   at::Tensor dpre_part, dwa_part, dba_part, gvb16, dal_part, att_flags;
@@ -249,7 +259,8 @@ struct Backward : BwdArgs {
                (knobs().dw_aug < 0 ? persistent : knobs().dw_aug != 0)),
         dw_split(NR % 4 == 0 ? 4 : (NR % 2 == 0 ? 2 : 1)),
         ldhs(dw_aug ? H + knobs().dw_pad : H), oh_main(have_x && !ds_ready),
-        guard_rows(!ds_ready && blog.defined() && blog.numel() == V), CPAD(ao.CPAD),
+        guard_rows(!ds_ready && blog.defined() && blog.numel() == V),
+        ls(ls_eps > 0.0 && has_xe), CPAD(ao.CPAD),
         att_mfma(has_att && att_mfma_ok((int)vdiv, (int)C, (int)A, (int)H, per_frame) &&
                  att_bwd_epi_ok((int)vdiv, (int)C, (int)H) && (KD / 64) % 2 == 0),
         att_fuse(att_fuse_on() && att_mfma && n_steps > 1 && ao.u_all.defined() &&
@@ -293,6 +304,14 @@ struct Backward : BwdArgs {
       TORCH_CHECK(logits16.scalar_type() == at::kBFloat16,
                   "decoder_backward: the saved rows must be the exp store (forward store_exp) "
                   "unless a dense dS is given");
+    }
+    TORCH_CHECK(ls_eps >= 0.0 && ls_eps < 1.0, "ls_eps must be in [0, 1)");
+    if (ls) {
+      TORCH_CHECK(!ds_ready, "label smoothing runs on the exp store, not with a dense dS");
+      TORCH_CHECK(ls_wbar.has_value() && ls_wbar->defined() && ls_wbar->is_cuda() &&
+                      ls_wbar->scalar_type() == at::kFloat && ls_wbar->is_contiguous() &&
+                      ls_wbar->numel() >= H + 1 && H % 8 == 0 && H <= 2048,
+                  "ls_wbar must be the forward's fp32 (>= H + 1) mean logit row and bias");
     }
     if (early) {
       TORCH_CHECK(out_wlog.scalar_type() == at::kFloat && out_wlog.is_contiguous() &&
@@ -381,6 +400,10 @@ struct Backward : BwdArgs {
     // (only the row counter fix[0] needs zeroing: the list entries are written
     // by vgrad_onehot before vgrad_fix reads them)
     if (guard_rows) fix = at::empty({1 + NR}, i32);
+    if (ls) {
+      ls_part = at::empty({ls_rowsum_blocks(NR, LS_GSUM_ROWS), H + 8}, f32);
+      ls_gs = at::empty({H + 8}, f32);
+    }
     if (fix.defined()) (void)hipMemsetAsync(fix.data_ptr(), 0, sizeof(int), st);
     dG_all = at::empty({n_steps, R, KD}, wx.options());
     dc = at::zeros({R, H}, f32);
@@ -420,7 +443,7 @@ struct Backward : BwdArgs {
                  has_xe ? dg_xe.size(1) : 0, guard_rows ? fix.data_ptr<int>() : nullptr,
                  ptr_or_null<float>(oh_a), ptr_or_null<int>(oh_ys), ptr_or_null<float>(oh_b),
                  ptr_or_null<int>(oh_yx), have_x ? dHd.data_ptr<float>() : nullptr,
-                 exp_zero_off ? 1 : 0};
+                 exp_zero_off ? 1 : 0, ls ? (float)ls_eps : 0.f};
     launch_vgrad_onehot(va, reinterpret_cast<uint16_t*>(buf.data_ptr()), ldl,
                         alpha.data_ptr<float>(), s);
     if (guard_rows)
@@ -428,7 +451,18 @@ struct Backward : BwdArgs {
                        reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(),
                        reinterpret_cast<uint16_t*>(buf.data_ptr()), ldl, alpha.data_ptr<float>(),
                        ptr_or_null<int>(fix_total), s);
+    // forward X: final here (the guard's rows recomputed), read next by the loop
+    if (ls && have_x) ls_shift(0, NR, s);
     stamp(STAMP_BWD_ONEHOT, s);
+  }
+
+  // label smoothing: the rows' weights eps dg_xe, and X_r += (eps dg_r / alpha_r) wbar
+  LsRowW ls_rows() const {
+    return LsRowW{dg_xe.data_ptr<float>(), dg_xe.size(1), (int)R, (float)ls_eps, nullptr};
+  }
+  void ls_shift(int64_t r0, int64_t nr, hipStream_t s) {
+    launch_ls_shift(dHd.data_ptr<float>(), alpha.data_ptr<float>(), ls_wbar->data_ptr<float>(),
+                    ls_rows(), r0, nr, (int)H, s);
   }
 
   // side (current): X = E' W, chunk by chunk; the reverse loop reads alpha X
@@ -439,6 +473,7 @@ struct Backward : BwdArgs {
       const int64_t r0 = dhd_chunks[ci][0] * R, nr = (dhd_chunks[ci][1] - dhd_chunks[ci][0]) * R;
       at::Tensor dst = dHd.narrow(0, r0, nr);
       if (!have_x) at::mm_out(dst, Ev.narrow(0, r0, nr), wlog, at::kFloat);
+      if (ls && !have_x) ls_shift(r0, nr, side.stream());
       (void)hipEventRecord(ev(EV_DHD_CHUNK0 + (int)ci), side.stream());
       if (ci == 0) stamp(STAMP_BWD_DHD0, side.stream());
     }
@@ -509,6 +544,15 @@ struct Backward : BwdArgs {
       launch_vgrad_colsum(reinterpret_cast<const uint16_t*>(buf.data_ptr()), ldl, (int)V, NR,
                           alpha.data_ptr<float>(), cs_part.data_ptr<float>(),
                           dblog.data_ptr<float>(), side.stream());
+    if (ls) {
+      // the uniform part: (1 / V) sum_r eps dg_r [Hd_r | 1] onto every row of
+      // dW_logit / entry of db_logit, once both are written
+      launch_ls_rowsum(reinterpret_cast<const uint16_t*>(hd2.data_ptr()), NR, (int)H, ls_rows(),
+                       LS_GSUM_ROWS, (float)(1.0 / (double)V), ls_part.data_ptr<float>(),
+                       ls_gs.data_ptr<float>(), side.stream());
+      launch_ls_add(dWlog.data_ptr<float>(), dblog.data_ptr<float>(), ls_gs.data_ptr<float>(),
+                    (int)V, (int)H, side.stream());
+    }
     (void)hipEventRecord(ev(EV_SIDE_DONE), side.stream());
     if (grad_ev) record_grad_event(aux.grad_ev[0], side.stream(), 0);
     if (early_comm)
@@ -993,11 +1037,12 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
                                          at::Tensor xw, std::vector<at::Tensor> vg_bwd,
                                          int64_t vg_nf, double vg_p, int64_t x_wait,
                                          bool exp_zero_off, std::vector<at::Tensor> dw_slots,
-                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C) {
+                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C,
+                                         double ls_eps, c10::optional<at::Tensor> ls_wbar) {
   Backward b(BwdArgs{wx, wlog, emb, lse, logits16, hdrop_all, gates_all, c_all, h_all, seq, labels,
                      toks, dg_sel, dg_xe, drop_p, rng, out_wlog, out_blog, comm_stream, att, out_emb,
                      ds_bias, cell, state0, up, blog, fix_total, vgate_div, xw, vg_bwd, vg_nf, vg_p,
-                     x_wait, exp_zero_off, dw_slots, vg_idx, vg_C});
+                     x_wait, exp_zero_off, dw_slots, vg_idx, vg_C, ls_eps, ls_wbar});
   const hipStream_t st = b.st, side = b.side.stream(), side2 = b.side2.stream();
 
   // main: operands; side2: the token sort, under X and the loop

@@ -21,6 +21,10 @@ struct Rollout {
   const std::vector<at::Tensor>&state0, &up;
   const bool store_exp, xe_rows;
   const c10::optional<at::Tensor>& lab_idx;
+  // label smoothing (kernels/label_smooth.hip): g_xe leaves as the smoothed
+  // target log-prob, ls_wbar receives the mean logit row / bias (backward)
+  const double ls_eps;
+  const c10::optional<at::Tensor>& ls_wbar;
   // ---- sizes and operands (check_args) --------------------------------------
   bool has_att = false, have_labels = false, have_idx = false;
   int64_t H4 = 0, H = 0, E = 0, V = 0, L = 0, n_steps = 0, NL = 1;
@@ -134,6 +138,29 @@ struct Rollout {
     // initial state (model_type 'standard': the state after the video step;
     // otherwise zero): state0 = {h0 bf16 (R, H), c0 fp32 (R, H)}
     s0 = InitState::parse(state0, Site::Forward, has_att, R, H);
+    TORCH_CHECK(ls_eps >= 0.0 && ls_eps < 1.0, "ls_eps must be in [0, 1)");
+    if (ls_eps > 0.0)
+      TORCH_CHECK(want_xe && save && store_exp && H % 8 == 0 && H <= 2048 && ls_wbar.has_value() &&
+                      ls_wbar->defined() && ls_wbar->is_cuda() &&
+                      ls_wbar->scalar_type() == at::kFloat && ls_wbar->is_contiguous() &&
+                      ls_wbar->numel() >= H + 1,
+                  "label smoothing: a saved exp-store forward with XE targets, H <= 2048 and an "
+                  "fp32 ls_wbar (>= H + 1)");
+  }
+
+  // label smoothing, after the last combine: the column mean of the bf16 logit
+  // weights the vocabulary tiles read (and the mean bias) into ls_wbar, then
+  // g_xe[r, t] = (1 - eps) lp[y] + eps (Hd . wbar + bbar - lse) from the saved
+  // vocab input: no dense pass
+  void smooth_xe() {
+    if (!(ls_eps > 0.0)) return;
+    at::Tensor lpart = at::empty({ls_rowsum_blocks(V, LS_WBAR_ROWS), H + 8}, f32);
+    launch_ls_rowsum(W, V, (int)H, LsRowW{nullptr, 0, 1, 0.f, blog.data_ptr<float>()},
+                     LS_WBAR_ROWS, (float)(1.0 / (double)V), lpart.data_ptr<float>(),
+                     ls_wbar->data_ptr<float>(), st);
+    launch_ls_blend(reinterpret_cast<const uint16_t*>(HDs[NL - 1].data_ptr()),
+                    ls_wbar->data_ptr<float>(), lse.data_ptr<float>(), n_steps * R, (int)R, (int)H,
+                    (float)ls_eps, g_xe.data_ptr<float>(), T, st);
   }
 
   void alloc() {
@@ -333,6 +360,7 @@ struct Rollout {
     g_xe.copy_(gxt);
     g_sel.copy_(gxt.narrow(1, 0, T - 1));
     seq.copy_(labels.narrow(1, 1, T - 1));
+    smooth_xe();
     stamp(STAMP_FWD_END, st);
     return {seq, g_sel, g_xe, lse, logits16, HDs[0], Gs[0], Cs[0], Hs[0]};
   }
@@ -434,6 +462,7 @@ struct Rollout {
     }
     if (conv_join)
       (void)hipStreamWaitEvent(st, device_aux((int)wx.device().index()).fwd_ev[1], 0);
+    smooth_xe();
     stamp(STAMP_FWD_END, st);
     // saved: {logits16, hd of the top layer (vocab input), layer 0's gates, c, h}
     // (+ {alpha_all, q_all, u_all}) (+ {h, c, gates of layer l, hd of layer l-1} per l >= 1)
@@ -473,10 +502,11 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
                                         bool use_unfinished, std::vector<at::Tensor> att,
                                         int64_t cell, std::vector<at::Tensor> state0,
                                         std::vector<at::Tensor> up, bool store_exp,
-                                        bool xe_rows, c10::optional<at::Tensor> lab_idx) {
+                                        bool xe_rows, c10::optional<at::Tensor> lab_idx,
+                                        double ls_eps, c10::optional<at::Tensor> ls_wbar) {
   Rollout r{wx, emb, ptab, whh, wlog, blog, vgate, vgate_div, labels, bos, R, T, modes, ss_prob,
             drop_p, temperature, rng, save, want_xe, use_counts, use_unfinished, att, cell, state0,
-            up, store_exp, xe_rows, lab_idx};
+            up, store_exp, xe_rows, lab_idx, ls_eps, ls_wbar};
   r.check_args();
   r.alloc();
   return xe_rows ? r.run_xe_rows() : r.run_steps();

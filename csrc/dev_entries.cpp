@@ -516,11 +516,18 @@ at::Tensor token_group_sum(at::Tensor x, at::Tensor toks, int64_t V) {
 // guard on.  forward_x: the one-hot weights / tokens are written out too, and
 // with the guard the listed rows of X (n R, H) fp32 (empty: zeros) recomputed.
 // Returns {alpha (n R), fix (1 + n R int32)[, oh_a, oh_ys, oh_b, oh_yx, X]}.
+// ls_eps > 0 (label smoothing, kernels/label_smooth.hip): dg_xe is the gradient
+// of the smoothed target log-prob -- the one-hot weight of the fold / oh_b is
+// (1 - ls_eps) dg_xe, alpha keeps the total weight --, and X (n R, H) fp32,
+// required then, gets the shift X_r += (ls_eps dg_r / alpha_r) ls_wbar[0 .. H)
+// after the fold and the guard (ls_wbar: fp32, >= H + 1); X is returned last
+// in every mode.
 std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_sel,
                                    at::Tensor dg_sel, at::Tensor labels, at::Tensor dg_xe,
                                    int64_t V, int64_t zero_off, at::Tensor hd, at::Tensor wlog,
                                    at::Tensor blog, at::Tensor fix_total, bool forward_x,
-                                   at::Tensor X) {
+                                   at::Tensor X, double ls_eps,
+                                   c10::optional<at::Tensor> ls_wbar) {
   check_cuda(E, "E");
   check_cuda(lse, "lse");
   TORCH_CHECK(E.scalar_type() == at::kBFloat16 && E.dim() == 3, "vgrad_fold: E (n, R, ldl) bf16");
@@ -583,6 +590,16 @@ std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_se
     }
   }
   const bool have_x = forward_x && guard;
+  const bool ls = ls_eps > 0.0;
+  if (ls) {
+    TORCH_CHECK(ls_eps < 1.0 && has_xe && X.defined() && X.is_cuda() &&
+                    X.scalar_type() == at::kFloat && X.dim() == 2 && X.size(0) == NR &&
+                    X.is_contiguous() && X.size(1) % 4 == 0 && (!guard || X.size(1) == H) &&
+                    ls_wbar.has_value() && ls_wbar->is_cuda() &&
+                    ls_wbar->scalar_type() == at::kFloat && ls_wbar->is_contiguous() &&
+                    ls_wbar->numel() >= X.size(1) + 1,
+                "vgrad_fold: ls_eps in (0, 1) needs dg_xe, X (n R, H) fp32 and ls_wbar (>= H + 1) fp32");
+  }
   VGradRows va{(int)R, (int)n, (int)T_sel, (int)H, (int)V, lse.data_ptr<float>(),
                has_sel ? y_sel.data_ptr<int64_t>() : nullptr,
                has_sel ? dg_sel.data_ptr<float>() : nullptr,
@@ -590,7 +607,7 @@ std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_se
                has_xe ? dg_xe.data_ptr<float>() : nullptr, has_xe ? dg_xe.stride(0) : 0,
                guard ? fix.data_ptr<int>() : nullptr, ptr_or_null<float>(oh_a),
                ptr_or_null<int>(oh_ys), ptr_or_null<float>(oh_b), ptr_or_null<int>(oh_yx),
-               have_x ? X.data_ptr<float>() : nullptr, zero_off ? 1 : 0};
+               have_x ? X.data_ptr<float>() : nullptr, zero_off ? 1 : 0, (float)ls_eps};
   hipStream_t st = cur_stream();
   launch_vgrad_onehot(va, reinterpret_cast<uint16_t*>(E.data_ptr()), ldl, alpha.data_ptr<float>(),
                       st);
@@ -599,11 +616,13 @@ std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_se
                      reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(),
                      reinterpret_cast<uint16_t*>(E.data_ptr()), ldl, alpha.data_ptr<float>(),
                      fix_total.data_ptr<int>(), st);
+  if (ls)
+    launch_ls_shift(X.data_ptr<float>(), alpha.data_ptr<float>(), ls_wbar->data_ptr<float>(),
+                    LsRowW{dg_xe.data_ptr<float>(), dg_xe.stride(0), (int)R, (float)ls_eps, nullptr},
+                    0, NR, (int)X.size(1), st);
   std::vector<at::Tensor> out{alpha, fix};
-  if (forward_x) {
-    out.insert(out.end(), {oh_a, oh_ys, oh_b, oh_yx});
-    if (guard) out.push_back(X);
-  }
+  if (forward_x) out.insert(out.end(), {oh_a, oh_ys, oh_b, oh_yx});
+  if (have_x || ls) out.push_back(X);
   return out;
 }
 
@@ -632,8 +651,73 @@ at::Tensor vgrad_rows(at::Tensor alpha, at::Tensor hd, int64_t ldhs, at::Tensor 
 }
 
 // bias-gradient column sums for tests: E (NR, ldl) bf16, alpha (NR) -> db (V) fp32
-at::Tensor vgrad_colsum(at::Tensor E, at::Tensor alpha, int64_t V) {
+// ls_mode (label smoothing's kernels, kernels/label_smooth.hip):
+//   1  column mean: E = the bf16 logit weights (V, H), alpha = the bias (V) ->
+//      (H + 8) fp32: the mean row, at [H] the mean bias (what the forward keeps)
+//   2  rank-1 sums: E = hd (n R, H) bf16, ls_dg = dg_xe (R, >= n) fp32 (its own
+//      row stride) -> (H + 8) fp32: (ls_eps / V) sum_r dg_r [hd_r | 1]; with
+//      ls_dw (V, H) / ls_db (V) fp32 also added onto them in place
+//   3  smoothed log-prob: E = hd (n R, H) bf16, alpha = lse (n R), ls_dw = the
+//      mode-1 vector, ls_dg = the target log-probs (R, n), blended in place:
+//      (1 - ls_eps) g + ls_eps (hd . wbar + bbar - lse); returns ls_dg
+at::Tensor vgrad_colsum(at::Tensor E, at::Tensor alpha, int64_t V, int64_t ls_mode, double ls_eps,
+                        c10::optional<at::Tensor> ls_dg, c10::optional<at::Tensor> ls_dw,
+                        c10::optional<at::Tensor> ls_db) {
   check_cuda(E, "E");
+  if (ls_mode != 0) {
+    TORCH_CHECK(ls_mode >= 1 && ls_mode <= 3 && E.scalar_type() == at::kBFloat16 && E.dim() == 2 &&
+                    E.is_contiguous() && E.size(0) > 0 && E.size(1) % 8 == 0 && E.size(1) <= 2048,
+                "vgrad_colsum: ls_mode 1..3 over contiguous bf16 rows (n, H), H % 8 == 0, H <= 2048");
+    const int64_t n = E.size(0), H = E.size(1);
+    auto f32 = at::TensorOptions().dtype(at::kFloat).device(E.device());
+    auto f32_cuda = [](const at::Tensor& t) {
+      return t.defined() && t.is_cuda() && t.scalar_type() == at::kFloat;
+    };
+    const uint16_t* rows = reinterpret_cast<const uint16_t*>(E.data_ptr());
+    hipStream_t st = cur_stream();
+    if (ls_mode == 1) {
+      TORCH_CHECK(f32_cuda(alpha) && alpha.is_contiguous() && alpha.numel() == n && V == n,
+                  "vgrad_colsum: ls_mode 1 takes the bias (V) fp32");
+      at::Tensor part = at::empty({ls_rowsum_blocks(n, LS_WBAR_ROWS), H + 8}, f32);
+      at::Tensor out = at::zeros({H + 8}, f32);
+      launch_ls_rowsum(rows, n, (int)H, LsRowW{nullptr, 0, 1, 0.f, alpha.data_ptr<float>()},
+                       LS_WBAR_ROWS, (float)(1.0 / (double)V), part.data_ptr<float>(),
+                       out.data_ptr<float>(), st);
+      return out;
+    }
+    TORCH_CHECK(ls_eps > 0.0 && ls_eps < 1.0 && ls_dg.has_value() && f32_cuda(*ls_dg) &&
+                    ls_dg->dim() == 2 && ls_dg->stride(1) == 1 && ls_dg->size(0) > 0 &&
+                    n % ls_dg->size(0) == 0 && ls_dg->size(1) >= n / ls_dg->size(0) &&
+                    ls_dg->stride(0) >= ls_dg->size(1),
+                "vgrad_colsum: ls_mode 2 / 3 take ls_eps in (0, 1) and ls_dg (R, >= n) fp32");
+    const int64_t R = ls_dg->size(0);
+    if (ls_mode == 2) {
+      TORCH_CHECK(V > 0, "vgrad_colsum: V");
+      at::Tensor part = at::empty({ls_rowsum_blocks(n, LS_GSUM_ROWS), H + 8}, f32);
+      at::Tensor out = at::zeros({H + 8}, f32);
+      launch_ls_rowsum(rows, n, (int)H,
+                       LsRowW{ls_dg->data_ptr<float>(), ls_dg->stride(0), (int)R, (float)ls_eps,
+                              nullptr},
+                       LS_GSUM_ROWS, (float)(1.0 / (double)V), part.data_ptr<float>(),
+                       out.data_ptr<float>(), st);
+      if (ls_dw.has_value() && ls_dw->defined() && ls_dw->numel() > 0) {
+        TORCH_CHECK(f32_cuda(*ls_dw) && ls_dw->is_contiguous() && ls_dw->dim() == 2 &&
+                        ls_dw->size(0) == V && ls_dw->size(1) == H && ls_db.has_value() &&
+                        f32_cuda(*ls_db) && ls_db->is_contiguous() && ls_db->numel() == V,
+                    "vgrad_colsum: ls_dw (V, H) / ls_db (V) fp32");
+        launch_ls_add(ls_dw->data_ptr<float>(), ls_db->data_ptr<float>(), out.data_ptr<float>(),
+                      (int)V, (int)H, st);
+      }
+      return out;
+    }
+    TORCH_CHECK(f32_cuda(alpha) && alpha.is_contiguous() && alpha.numel() == n &&
+                    ls_dw.has_value() && f32_cuda(*ls_dw) && ls_dw->is_contiguous() &&
+                    ls_dw->numel() >= H + 1,
+                "vgrad_colsum: ls_mode 3 takes lse (n R) and the mean row (>= H + 1) fp32");
+    launch_ls_blend(rows, ls_dw->data_ptr<float>(), alpha.data_ptr<float>(), n, (int)R, (int)H,
+                    (float)ls_eps, ls_dg->data_ptr<float>(), ls_dg->stride(0), st);
+    return *ls_dg;
+  }
   check_cuda(alpha, "alpha");
   TORCH_CHECK(E.scalar_type() == at::kBFloat16 && E.dim() == 2 &&
                   alpha.scalar_type() == at::kFloat && alpha.numel() == E.size(0) &&

@@ -20,7 +20,8 @@ std::vector<at::Tensor> decoder_forward(at::Tensor wx, at::Tensor emb, at::Tenso
                                         bool use_unfinished, std::vector<at::Tensor> att,
                                         int64_t cell, std::vector<at::Tensor> state0,
                                         std::vector<at::Tensor> up, bool store_exp,
-                                        bool xe_rows, c10::optional<at::Tensor> lab_idx);
+                                        bool xe_rows, c10::optional<at::Tensor> lab_idx,
+                                        double ls_eps, c10::optional<at::Tensor> ls_wbar);
 std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Tensor emb,
                                          at::Tensor lse, at::Tensor logits16,
                                          at::Tensor hdrop_all, at::Tensor gates_all,
@@ -36,7 +37,8 @@ std::vector<at::Tensor> decoder_backward(at::Tensor wx, at::Tensor wlog, at::Ten
                                          at::Tensor xw, std::vector<at::Tensor> vg_bwd,
                                          int64_t vg_nf, double vg_p, int64_t x_wait,
                                          bool exp_zero_off, std::vector<at::Tensor> dw_slots,
-                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C);
+                                         c10::optional<at::Tensor> vg_idx, int64_t vg_C,
+                                         double ls_eps, c10::optional<at::Tensor> ls_wbar);
 std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor whh,
                                     at::Tensor wlog, at::Tensor blog, at::Tensor vgate,
                                     int64_t K, int64_t T, int64_t bos_index,
@@ -147,9 +149,12 @@ std::vector<at::Tensor> vgrad_fold(at::Tensor E, at::Tensor lse, at::Tensor y_se
                                    at::Tensor dg_sel, at::Tensor labels, at::Tensor dg_xe,
                                    int64_t V, int64_t zero_off, at::Tensor hd, at::Tensor wlog,
                                    at::Tensor blog, at::Tensor fix_total, bool forward_x,
-                                   at::Tensor X);
+                                   at::Tensor X, double ls_eps,
+                                   c10::optional<at::Tensor> ls_wbar);
 at::Tensor vgrad_rows(at::Tensor alpha, at::Tensor hd, int64_t ldhs, at::Tensor dhd);
-at::Tensor vgrad_colsum(at::Tensor E, at::Tensor alpha, int64_t V);
+at::Tensor vgrad_colsum(at::Tensor E, at::Tensor alpha, int64_t V, int64_t ls_mode, double ls_eps,
+                        c10::optional<at::Tensor> ls_dg, c10::optional<at::Tensor> ls_dw,
+                        c10::optional<at::Tensor> ls_db);
 at::Tensor video_gate_grad(at::Tensor dG, int64_t vdiv, int64_t G4);
 at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K);
 void wgrad_tn_rows(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K, at::Tensor out,

@@ -24,6 +24,15 @@
 // (The XE all-rows forward, decoder_forward.cpp, writes E = exp(x) with c = 0 for every
 // row: VGradRows::zero_off, s_r = exp(-lse_r), guarded for |lse_r| > 60.)
 //
+// Label smoothing (VGradRows::ls_eps; label_smooth.hip): the XE weight arrives
+// as the gradient g of the smoothed log-prob, dS_rv = (1 - eps) g [v = yx] +
+// eps g / V - g p_rv.  alpha keeps the total weight, -(a + g) s; the one-hot
+// weight b (the fold here, oh_b for the loop) is (1 - eps) g; the uniform
+// part is added by label_smooth.hip's rank-1 kernels.  (A row whose
+// sampled-token weight cancels the target's exactly, a = -g on one token, has
+// alpha = 0 and carries no uniform term either: no loss of the recipes weights
+// both tokens of a row.)
+//
 // Range of the exp store: E = exp(x - c) with c = the previous step's LSE
 // stays inside bf16 (fp32's exponent range) while the row's LSE moves by
 // less than ~80 between steps (overflow above, loss of the row's mass to
@@ -56,6 +65,9 @@ __device__ __forceinline__ RowW row_weights(const VGradRows& g, int64_t row, boo
         : t > 0      ? __expf(g.lse[(int64_t)(t - 1) * g.R + r] - g.lse[row])
                      : 1.f;
   w.al = -(w.a + w.b) * w.s;
+  // label smoothing (label_smooth.hip): alpha from the total weight a + dg_xe
+  // (above), the one-hot weight scaled by 1 - eps
+  if (g.ls_eps != 0.f) w.b *= 1.f - g.ls_eps;
   // weights that (nearly) cancel on two different tokens: keep alpha away from
   // 0 so the one-hot terms stay representable (ys == yx cancels exactly)
   if (w.a != 0.f && w.b != 0.f && w.ys >= 0 && w.yx >= 0 && w.ys != w.yx) {

@@ -351,6 +351,10 @@ struct VGradRows {
   // of exp(x - the previous step's LSE): s = exp(-lse), and the range guard
   // lists rows with |lse| > EXP_SAFE_LSE_JUMP (step 0 included)
   int zero_off;
+  // label smoothing (label_smooth.hip): dg_xe is the gradient of the SMOOTHED
+  // target log-prob, so the one-hot weight b is (1 - ls_eps) dg_xe while alpha
+  // keeps the total weight -(a + dg_xe) s.  0: off, every operand as before
+  float ls_eps;
 };
 constexpr float EXP_SAFE_LSE_JUMP = 60.f;
 // alpha (NR) and the one-hot terms folded into E (NR rows, stride ldl), in place
@@ -372,6 +376,32 @@ void launch_vgrad_rows(const float* alpha, int64_t NR, int H, const uint16_t* hd
 int vgrad_colsum_blocks(int64_t NR);
 void launch_vgrad_colsum(const uint16_t* E, int64_t ldl, int V, int64_t NR, const float* alpha,
                          float* part, float* dblog, hipStream_t stream);
+
+// label_smooth.hip: the uniform part of the smoothed XE target (see that file).
+// Row weights of the weighted row sums / the X shift: eps dg[r, t] of row
+// t R + r (dg: row stride rs), or (dg null; row sums only) weight 1 with the
+// extra term bias[row]
+struct LsRowW {
+  const float* dg;
+  int64_t rs;
+  int R;
+  float eps;
+  const float* bias;
+};
+// out (H + 1) = scale * (sum_r w_r rows[r, :], sum_r extra_r), two-stage and
+// deterministic; rb rows per block, part: ls_rowsum_blocks(n, rb) * (H + 8) floats
+int ls_rowsum_blocks(int64_t n, int rb);
+void launch_ls_rowsum(const uint16_t* rows, int64_t n, int H, const LsRowW& w, int rb, float scale,
+                      float* part, float* out, hipStream_t stream);
+constexpr int LS_WBAR_ROWS = 64, LS_GSUM_ROWS = 128;  // rows per block: column mean / rank-1 sums
+// g_xe[r, t] (row stride g_rs) = (1 - eps) g_xe[r, t] + eps (hd[t R + r] . wbar + wbar[H] - lse)
+void launch_ls_blend(const uint16_t* hd, const float* wbar, const float* lse, int64_t NR, int R,
+                     int H, float eps, float* g_xe, int64_t g_rs, hipStream_t stream);
+// X[row] += (eps dg_row / alpha_row) wbar for rows [row0, row0 + nrows) with dg, alpha != 0
+void launch_ls_shift(float* X, const float* alpha, const float* wbar, const LsRowW& w,
+                     int64_t row0, int64_t nrows, int H, hipStream_t stream);
+// dW (V, H) += gs[0 .. H) per row, db (V) += gs[H]
+void launch_ls_add(float* dW, float* db, const float* gs, int V, int H, hipStream_t stream);
 
 // lstm.hip
 // Words the first launch of a decode initialises for the combines that follow

@@ -50,6 +50,17 @@ def ema_decay_arg(spec):
     return d
 
 
+def label_smoothing_arg(spec):
+    """``--label_smoothing``: a finite float in [0, 1); 0 = plain cross-entropy."""
+    try:
+        e = float(spec)
+    except ValueError:
+        raise argparse.ArgumentTypeError('not a number: %r' % spec)
+    if not 0.0 <= e < 1.0:  # (NaN fails the comparison too)
+        raise argparse.ArgumentTypeError('--label_smoothing must be in [0, 1), got %r' % spec)
+    return e
+
+
 RL_OBJECTIVES = ('reinforce', 'risk', 'softmax_margin', 'multi_margin')
 
 
@@ -233,6 +244,12 @@ def build_parser():
              'the fused Adam pass, and validate / select / save the best checkpoint with it '
              '(the _last.pth sidecar keeps the live weights, the EMA in its optimizer state).  '
              '0 (default): off')
+    add('--label_smoothing', type=label_smoothing_arg, default=0.0, metavar='E',
+        help='label smoothing of the XE training loss (XE epochs, also those before '
+             '--use_rl_after): per token -[(1 - E) log p(y) + E mean_v log p(v)], the definition '
+             'of torch cross_entropy(label_smoothing=E); on the fused engine its uniform part '
+             'rides the exp-store backward as rank-1 terms (no dense log-probs).  RL / WXE '
+             'losses, the validation loss and every decode ignore it.  0 (default): off')
     add('--rl_objective', type=str, default='reinforce', choices=list(RL_OBJECTIVES),
         help='RL objective: reinforce (default) = REINFORCE with the baseline of the recipe '
              '(SCST / CST); risk, softmax_margin, multi_margin = sequence-level structured losses '

@@ -28,7 +28,25 @@ def reward_mask(seq):
     return torch.cat([m.new_ones(m.size(0), 1), m[:, :-1]], 1)
 
 
+def check_label_smoothing(eps):
+    """Validated ``--label_smoothing``: a finite float in [0, 1)."""
+    eps = float(eps)
+    if not 0.0 <= eps < 1.0:  # (NaN fails the comparison too)
+        raise ValueError('label_smoothing must be in [0, 1), got %r' % eps)
+    return eps
+
+
 class CrossEntropyCriterion(nn.Module):
+    """``label_smoothing`` eps (``--label_smoothing``, the definition of
+    ``F.cross_entropy(..., label_smoothing=eps)``): the per-token log-prob
+    becomes ``(1 - eps) lp[y] + eps mean_v lp[v]``.  Applied to dense
+    ``(N, T, V)`` log-probs only: gathered ``(N, T)`` input is what the fused
+    engine returns, already smoothed (``DecoderEngine.teacher_forced``)."""
+
+    def __init__(self, label_smoothing=0.0):
+        super().__init__()
+        self.label_smoothing = check_label_smoothing(label_smoothing)
+
     def forward(self, pred, target, mask):
         """pred: (N, T, V) log-probs, or (N, T) log-probs already gathered at
         ``target``."""
@@ -36,6 +54,9 @@ class CrossEntropyCriterion(nn.Module):
         target = target[:, :T]
         mask = mask[:, :T].float()
         lp = pred if pred.dim() == 2 else pred.gather(2, target.unsqueeze(2)).squeeze(2)
+        eps = self.label_smoothing
+        if eps > 0.0 and pred.dim() == 3:
+            lp = (1.0 - eps) * lp + eps * pred.mean(2)
         return -(lp * mask).sum() / mask.sum()
 
 

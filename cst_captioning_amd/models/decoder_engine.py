@@ -155,9 +155,21 @@ class _DecoderFn(torch.autograd.Function):
     def forward(ctx, vgate, w_ih, w_hh, emb_w, logit_w, logit_b, att_gv, att_pre, att_wq,
                 att_wa, att_ba, h0, c0, eng, labels, bos, R, T, modes, ss_prob, drop_p,
                 temperature, rng, vdiv, want_xe, use_counts, use_unfinished, save, want_full,
-                *up_w):
+                ls_eps, *up_w):
         has_att = att_gv is not None
         dev = logit_b.device
+        # label smoothing (csrc/kernels/label_smooth.hip): g_xe leaves the
+        # engine as the smoothed target log-prob; the forward fills ls_wbar
+        # (mean logit row, mean bias) and the backward takes it back
+        ls_eps = float(ls_eps)
+        ls_kw = {}
+        if ls_eps > 0.0:
+            if not (want_xe and save and not want_full):
+                raise RuntimeError('label smoothing needs a training teacher-forced forward '
+                                   '(XE targets, saved activations, gathered log-probs)')
+            ls_kw = dict(ls_eps=ls_eps,
+                         ls_wbar=torch.empty(eng.H + 8, dtype=torch.float32, device=dev))
+        ctx.ls_kw = ls_kw
         # labels by index (data/dataset.py IndexedLabels): the resident label
         # table + the call's rows of it; the kernels read the rows themselves
         lab_idx = None
@@ -189,7 +201,7 @@ class _DecoderFn(torch.autograd.Function):
             labels if labels is not None else torch.empty(0, dtype=torch.long),
             bos if bos is not None else torch.empty(0, dtype=torch.long), R, T, modes, ss_prob,
             drop_p, temperature, rng, save, want_xe, use_counts, use_unfinished, att, eng.cell,
-            state0, eng.upper_operands(), store_exp, xe_rows, lab_idx)
+            state0, eng.upper_operands(), store_exp, xe_rows, lab_idx, **ls_kw)
         ctx.xe_rows = xe_rows
         ctx.lab_idx = lab_idx
         xw = torch.empty(0, device=dev)  # X = E W: engine.launch_x after the rollout
@@ -344,7 +356,9 @@ class _DecoderFn(torch.autograd.Function):
             ctx.drop_p, ctx.rng, out_w, out_b, comm, att, out_emb, ds_bias, eng.cell,
             ctx.state0, eng.upper_operands(ctx.up_saved), ctx.logit_b, eng.exp_fix_rows,
             vdiv, xw if ctx.store_exp else empty, vg_bwd, vg_nf, float(vg_p),
-            0 if x_ev is None else int(x_ev.cuda_event), ctx.xe_rows, dw_slots, vg_idx, vg_C)
+            0 if x_ev is None else int(x_ev.cuda_event), ctx.xe_rows, dw_slots, vg_idx, vg_C,
+            **ctx.ls_kw)
+        ctx.ls_kw = {}
         ctx.logit_b = None
         ctx.up_saved = None
         d_up = []
@@ -379,10 +393,10 @@ class _DecoderFn(torch.autograd.Function):
             d_gv, d_pre, d_wa, d_ba, d_wq = res[5:10]
             d_wa, d_ba = d_wa.view(ctx.att_shapes[0]), d_ba.view(ctx.att_shapes[1])
             return (None, d_wih, d_whh, d_emb, dWlog, dblog, d_gv, d_pre, d_wq, d_wa,
-                    d_ba) + (None,) * 18
+                    d_ba) + (None,) * 19
         d_vgate = dvg  # (R // vdiv, 4H): summed over steps and each video's rows
         return (d_vgate, d_wih, d_whh, d_emb, dWlog, dblog) + (None,) * 5 + d_state + \
-            (None,) * 16 + tuple(d_up)
+            (None,) * 17 + tuple(d_up)
 
 
 _AUX = {}
@@ -834,7 +848,7 @@ class DecoderEngine:
 
     def _run(self, model, feats, labels, modes, want_xe, use_counts, use_unfinished,
              expand=True, ss_prob=0.0, drop=True, temperature=1.0, bos_rows=None,
-             want_full=False, rows_per_video=None):
+             want_full=False, rows_per_video=None, label_smoothing=0.0):
         if self.attention:
             att, B = self._att_inputs(model, feats)
             vg = None
@@ -873,7 +887,7 @@ class DecoderEngine:
                                 T,
                                 modes, float(ss_prob), float(drop_p), float(temperature),
                                 self._rng(m.logit.bias.device), S, want_xe, use_counts,
-                                use_unfinished, save, want_full, *ups)
+                                use_unfinished, save, want_full, float(label_smoothing), *ups)
 
     # -- public entry points ------------------------------------------------------
     def rollout(self, model, feats, labels):
@@ -886,13 +900,22 @@ class DecoderEngine:
                                      use_unfinished=mask_eos, ss_prob=model.ss_prob)
         return seq, g_sel, None
 
-    def teacher_forced(self, model, feats, labels):
+    def teacher_forced(self, model, feats, labels, label_smoothing=0.0):
         """Gathered log-probs of the GT targets ``labels[:, 1:]`` (R, T) --
-        what CrossEntropyCriterion needs.  Honours scheduled sampling."""
+        what CrossEntropyCriterion needs.  Honours scheduled sampling.
+        ``label_smoothing`` eps in (0, 1) (a training forward): the smoothed
+        quantity ``(1 - eps) lp[y] + eps mean_v lp[v]`` instead, which the same
+        criterion turns into the label-smoothed cross-entropy; its uniform
+        part rides the exp-store backward as rank-1 terms
+        (``csrc/kernels/label_smooth.hip``).  0: exactly the call without it."""
+        label_smoothing = float(label_smoothing)
+        if not 0.0 <= label_smoothing < 1.0:  # (NaN fails the comparison too)
+            raise ValueError('label_smoothing must be in [0, 1), got %r' % label_smoothing)
         T = labels.size(1) - 1
         modes = self._modes(model, T, rl=False)
         _, _, g_xe, _ = self._run(model, feats, labels, modes, want_xe=True, use_counts=True,
-                                  use_unfinished=False, ss_prob=model.ss_prob)
+                                  use_unfinished=False, ss_prob=model.ss_prob,
+                                  label_smoothing=label_smoothing)
         return g_xe
 
     def _modes(self, model, T, rl=True):

@@ -145,7 +145,14 @@ class Trainer:
         self.ctx = ctx or DistContext()
         self.engine = engine
         self.device = self.ctx.device
-        self.xe_criterion = CrossEntropyCriterion()
+        # --label_smoothing: the XE training loss only (xe_loss); the validation
+        # loss and the RL / WXE losses stay as they are
+        self.label_smoothing = float(getattr(opt, 'label_smoothing', 0.0) or 0.0)
+        self.xe_criterion = CrossEntropyCriterion(self.label_smoothing)
+        self.val_criterion = CrossEntropyCriterion()  # (validation Loss: plain NLL)
+        self._ls_rl_logged = False
+        if self.label_smoothing > 0.0:
+            logger.info('Label smoothing %g on the XE training loss', self.label_smoothing)
         self.rl_criterion = RewardCriterion()
         self.group_criterion = self._build_group_criterion()  # (--rl_objective)
         self.ctx.broadcast_module(model)
@@ -335,6 +342,10 @@ class Trainer:
 
     def rl_loss(self, data, scb_captions):
         opt = self.opt
+        if self.label_smoothing > 0.0 and not self._ls_rl_logged:
+            self._ls_rl_logged = True
+            logger.info('--label_smoothing applies to the XE loss only: the RL / WXE loss '
+                        'ignores it')
         S = self.train_loader.get_seq_per_img()
         scorer = self._ensure_scorer()
         vid_rows = data['video_index'].repeat_interleave(S)
@@ -455,7 +466,8 @@ class Trainer:
 
     def xe_loss(self, data):
         if self.engine is not None:
-            lp = self.engine.teacher_forced(self.model, self._feats(data), data['labels'])
+            lp = self.engine.teacher_forced(self.model, self._feats(data), data['labels'],
+                                            label_smoothing=self.label_smoothing)
             self.timer.mark('rollout')
             # (a batch whose masks were not set by hand: the loader's caption
             # masks, derived from the labels)
@@ -999,10 +1011,10 @@ class Trainer:
         m = self.model
         if self.engine is not None:
             lp = self.engine.teacher_forced(m, data['feats'], data['labels'])
-            loss = self.xe_criterion(lp, data['labels'][:, 1:], data['masks'][:, 1:])
+            loss = self.val_criterion(lp, data['labels'][:, 1:], data['masks'][:, 1:])
             return loss, data['labels'][:, 1:lp.size(1) + 1], lp
         pred, gt_seq, gt_lp = m(data['feats'], data['labels'])
-        loss = self.xe_criterion(pred, data['labels'][:, 1:], data['masks'][:, 1:])
+        loss = self.val_criterion(pred, data['labels'][:, 1:], data['masks'][:, 1:])
         return loss, gt_seq, gt_lp
 
     @staticmethod
