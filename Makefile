@@ -81,6 +81,10 @@ REWARD_MIX?=
 DECODE?=standard
 MBR_SAMPLES?=20
 MBR_TEMPERATURE?=1.0
+# truncated sampling of those samples: the MBR_TOP_K most probable words, the
+# nucleus MBR_TOP_P inside them (0 / 1.0: plain sampling)
+MBR_TOP_K?=0
+MBR_TOP_P?=1.0
 # the utility of consensus decoding in the grammar of REWARD_MIX, e.g.
 # MBR_MIX=CIDEr:1,Bleu_4:5,ROUGE_L:5 (empty: CIDEr-D); passed only when set
 MBR_MIX?=
@@ -193,6 +197,7 @@ TRAIN_OPT=--beam_size $(BEAM_SIZE) --max_patience $(MAX_PATIENCE) --eval_metric 
 	--use_cst $(USE_CST) --scb_captions $(SCB_CAPTIONS) --scb_baseline $(SCB_BASELINE) \
 	--loglevel $(LOGLEVEL) --model_type $(MODEL_TYPE) --use_eos $(USE_EOS) \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
+	--mbr_top_k $(MBR_TOP_K) --mbr_top_p $(MBR_TOP_P) \
 	$(if $(REWARD_MIX),--reward_mix $(REWARD_MIX)) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX)) \
 	--ema_decay $(EMA_DECAY) --label_smoothing $(LABEL_SMOOTHING) \
 	--rl_objective $(RL_OBJECTIVE) --rl_alpha $(RL_ALPHA) --rl_cost_scale $(RL_COST_SCALE) \
@@ -208,6 +213,7 @@ endif
 TEST_OPT=--beam_size $(BEAM_SIZE) --language_eval $(VAL_LANG_EVAL) --test_seq_per_img $(TEST_SEQ_PER_IMG) \
 	--test_batch_size $(BATCH_SIZE) --loglevel $(LOGLEVEL) --result_file $@ \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
+	--mbr_top_k $(MBR_TOP_K) --mbr_top_p $(MBR_TOP_P) \
 	$(MBR_TEST_OPT) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX))
 
 train: $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth

@@ -1,7 +1,164 @@
-// beam_search: batched beam search of the decoder executor.
+// beam_search: batched beam search of the decoder executor, and the truncated
+// (top-k / nucleus) sampling decode that shares its general step.
 #include "engine_internal.h"
 
 namespace cst {
+
+namespace {
+
+// The rows of one decode chain -- B videos x `rows` rows per video -- and the
+// part of a decode step that beam search and truncated sampling share: the
+// cell step(s) from the current input tokens (each row's state taken from row
+// parent[r] when a parent map is given), attention where present, and the
+// vocab launch that leaves each 128-column tile's `ktop` best (logit, index)
+// pairs per row (VF_TOPK, ktop <= 8) or the fp32 logits.
+struct DecodeRows {
+  const at::Tensor &wx, &ptab, &whh, &wlog, &blog, &vgate;
+  const int64_t rows, ktop, cell;
+  const int64_t H4, H, V, B, R, ldl;
+  const int n_vt;
+  const bool tile_topk;
+  const AttOperands ao;
+  const bool has_att;
+  const UpperLayers upl;
+  const int64_t NL;
+  at::TensorOptions f32, i64, i32;
+  hipStream_t st;
+  at::Tensor logits, lse, part, tok, vg_rows, qb, xin;
+  std::vector<std::array<at::Tensor, 2>> hl, cl;
+
+  DecodeRows(const at::Tensor& wx_, const at::Tensor& ptab_, const at::Tensor& whh_,
+             const at::Tensor& wlog_, const at::Tensor& blog_, const at::Tensor& vgate_,
+             int64_t rows_, int64_t ktop_, int64_t bos_index, const std::vector<at::Tensor>& att,
+             int64_t cell_, const std::vector<at::Tensor>& state0,
+             const std::vector<at::Tensor>& up)
+      : wx(wx_), ptab(ptab_), whh(whh_), wlog(wlog_), blog(blog_), vgate(vgate_), rows(rows_),
+        ktop(ktop_), cell(cell_), H4(wx_.size(0)), H(H4 / 4), V(wlog_.size(0)), B(vgate_.size(0)),
+        R(B * rows_), ldl((V + 7) / 8 * 8), n_vt(vocab_num_tiles((int)V)),
+        // ktop <= 8: the vocab launch keeps each tile's best logits per row
+        // (VF_TOPK) and the selection merges n_vt * ktop candidates -- no R x V
+        // fp32 logits
+        tile_topk(ktop_ <= 8),
+        // temporal attention: att = {Gv, P, W_q, w_a, b_a} as in decoder_forward
+        ao(AttOperands::parse(att, Site::Beam, H, R, rows_, 0)), has_att(ao.on),
+        // stacked layers: up = {[W_ih | W_hh] (4H, 2H), W_hh (4H, H)} per upper layer
+        upl(UpperLayers::parse(up, Site::Beam, has_att, !state0.empty(), H, 0)), NL(upl.NL) {
+    auto dev = wx.device();
+    f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
+    i64 = at::TensorOptions().dtype(at::kLong).device(dev);
+    i32 = at::TensorOptions().dtype(at::kInt).device(dev);
+    st = cur_stream();
+    logits = tile_topk ? at::empty({(int64_t)n_vt * R * ktop * 2}, f32) : at::empty({R, ldl}, f32);
+    lse = at::empty({R}, f32);
+    part = at::empty({(int64_t)n_vt * R * vocab_partial_bytes() / 4}, f32);
+    tok = at::full({R}, bos_index, i64);
+    hl.resize(NL), cl.resize(NL);
+    for (int64_t l = 0; l < NL; ++l) {
+      hl[l] = {at::zeros({R, H}, wx.options()), at::empty({R, H}, wx.options())};
+      cl[l] = {at::zeros({R, H}, f32), at::empty({R, H}, f32)};
+    }
+    xin = NL > 1 ? at::empty({R, H4}, f32) : at::Tensor();
+    const InitState s0 = InitState::parse(state0, Site::Beam, has_att, B, H);
+    if (s0.on) {  // per-video initial state {h0 (B, H), c0 (B, H)}, one copy per row
+      hl[0][0].copy_(s0.h0.repeat_interleave(rows, 0));
+      cl[0][0].copy_(s0.c0.repeat_interleave(rows, 0));
+    }
+    if (has_att) {
+      vg_rows = at::empty({R, H4}, f32);
+      qb = at::empty({R, ao.A}, f32);
+    }
+  }
+
+  // step t of the chain: state parity t -> t + 1, then the vocab launch on the
+  // top layer's new h; `combine`: the row LSE into `lse` as a launch of its own
+  void step(int64_t t, const int* parent, bool combine) {
+    const uint16_t* W = reinterpret_cast<const uint16_t*>(wlog.data_ptr());
+    const uint16_t* WHH = reinterpret_cast<const uint16_t*>(whh.data_ptr());
+    const at::Tensor& hp = hl[0][t & 1];
+    const at::Tensor& cp = cl[0][t & 1];
+    at::Tensor& ho = hl[0][(t + 1) & 1];
+    at::Tensor& co = cl[0][(t + 1) & 1];
+    if (has_att) {
+      if (t >= 1) at::mm_out(qb, hp, ao.wq.t(), at::kFloat);
+      launch_att_fwd(ao.gv.data_ptr<float>(), ao.pre.data_ptr<float>(),
+                     t >= 1 ? qb.data_ptr<float>() : nullptr, parent,
+                     ao.wa.data_ptr<float>(), ao.ba.data_ptr<float>(), (int)B, (int)rows, (int)ao.C,
+                     (int)ao.A, (int)H4, vg_rows.data_ptr<float>(), nullptr, st, 0, ao.per_frame);
+    }
+    launch_lstm_step_fwd(tok.data_ptr<int64_t>(), 1, reinterpret_cast<const uint16_t*>(ptab.data_ptr()),
+                         reinterpret_cast<const uint16_t*>(hp.data_ptr()), cp.data_ptr<float>(),
+                         has_att ? vg_rows.data_ptr<float>() : vgate.data_ptr<float>(),
+                         has_att ? 1 : (int)rows, (int)R, (int)H, WHH,
+                         reinterpret_cast<uint16_t*>(ho.data_ptr()), co.data_ptr<float>(), nullptr,
+                         (int)H, 0.f, nullptr, (int)t, nullptr, st, parent, (int)cell);
+    for (int64_t l = 1; l < NL; ++l) {  // upper layers: their state follows the parent row too
+      at::mm_out(xin, hl[l - 1][(t + 1) & 1], upl(l, 0).narrow(1, 0, H).t(), at::kFloat);
+      launch_lstm_step_fwd(nullptr, 0, nullptr,
+                           reinterpret_cast<const uint16_t*>(hl[l][t & 1].data_ptr()),
+                           cl[l][t & 1].data_ptr<float>(), xin.data_ptr<float>(), 1, (int)R,
+                           (int)H, reinterpret_cast<const uint16_t*>(upl(l, 1).data_ptr()),
+                           reinterpret_cast<uint16_t*>(hl[l][(t + 1) & 1].data_ptr()),
+                           cl[l][(t + 1) & 1].data_ptr<float>(), nullptr, (int)H, 0.f, nullptr,
+                           (int)t, nullptr, st, parent, (int)cell);
+    }
+    const at::Tensor& htop = hl[NL - 1][(t + 1) & 1];
+    launch_vocab_fwd(reinterpret_cast<const uint16_t*>(htop.data_ptr()), (int)H, (int)R, (int)H, W,
+                     blog.data_ptr<float>(), (int)V,
+                     reinterpret_cast<uint16_t*>(logits.data_ptr()), ldl, part.data_ptr(),
+                     nullptr, 0, tile_topk ? (VF_TOPK_H | ((int)ktop << 8)) : /*fp32 logits*/ 8, 1.f,
+                     nullptr, (int)t, st);
+    if (combine)
+      launch_vocab_combine(part.data_ptr(), n_vt, (int)R, lse.data_ptr<float>(), nullptr, 0,
+                           nullptr, 0, nullptr, 0, nullptr, 0, SEL_GT_H, 0.f, nullptr, (int)t,
+                           nullptr, 0, nullptr, st);
+  }
+};
+
+// Truncated sampling decode (CaptionModel.sample with top_k in [1, 8]) for B
+// videos x S rows per video with the operands of beam_search: per step the
+// cell step(s) -- every row continues its own state, no parent map --,
+// attention where present, the VF_TOPK vocab launch with K = top_k and the
+// selection launch (kernels/topk_sample.hip: LSE, global top-K, temperature,
+// nucleus, draw, end-of-sequence rule).  Three launches per step for a
+// one-layer decoder without attention; no host synchronisation and a fixed
+// launch count.  rng: int32[2] device seeds, slot 1 keys the draws.  Returns
+// {seq (R, T - 2) int64, logprobs (R, T - 2) fp32}, T = seq_length: the
+// width of the sampler of decoder_forward, zeros after a row's end.
+std::vector<at::Tensor> sample_topk(const at::Tensor& wx, const at::Tensor& ptab,
+                                    const at::Tensor& whh, const at::Tensor& wlog,
+                                    const at::Tensor& blog, const at::Tensor& vgate,
+                                    int64_t top_k, int64_t T, int64_t bos_index,
+                                    const std::vector<at::Tensor>& att, int64_t cell,
+                                    const std::vector<at::Tensor>& state0,
+                                    const std::vector<at::Tensor>& up, int64_t S, double top_p,
+                                    double temperature, const at::Tensor& rng) {
+  TORCH_CHECK(top_k >= 1 && top_k <= 8, "top_k must be in [1, 8] on the engine");
+  TORCH_CHECK(top_k <= wlog.size(0), "top_k > vocab_size");
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, "top_p must be in (0, 1]");
+  TORCH_CHECK(temperature > 0.0 && std::isfinite(temperature), "temperature must be positive");
+  TORCH_CHECK(T >= 3, "seq_length must be at least 3");
+  DecodeRows d(wx, ptab, whh, wlog, blog, vgate, S, top_k, bos_index, att, cell, state0, up);
+  const int64_t R = d.R, Ts = T - 2;
+  at::Tensor seq = at::zeros({R, Ts}, d.i64);
+  at::Tensor lp = at::zeros({R, Ts}, d.f32);
+  at::Tensor unfinished = at::ones({R}, d.f32.dtype(at::kByte));
+  for (int64_t t = 0; t < T - 1; ++t) {
+    if (t >= 1) {
+      TopkSampleArgs sa{reinterpret_cast<const VocabPartial*>(d.part.data_ptr()),
+                        reinterpret_cast<const float2*>(d.logits.data_ptr()), d.n_vt, (int)R,
+                        (int)top_k, (int)d.V, (float)top_p, (float)(1.0 / temperature),
+                        rng_ptr(rng), (int)t, unfinished.data_ptr<uint8_t>(),
+                        seq.data_ptr<int64_t>() + (t - 1), Ts, d.tok.data_ptr<int64_t>(),
+                        lp.data_ptr<float>() + (t - 1), Ts, nullptr};
+      launch_topk_sample(sa, d.st);
+      if (t == T - 2) break;  // the last cell step would feed nothing
+    }
+    d.step(t, nullptr, /*combine=*/false);
+  }
+  return {seq, lp};
+}
+
+}  // namespace
 
 // Batched beam search (reference sample_beam, model.py:369-512) for B videos
 // x K beams, entirely on the GPU: per step one LSTM launch (h/c of each row's
@@ -13,32 +170,30 @@ std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor w
                                     at::Tensor wlog, at::Tensor blog, at::Tensor vgate,
                                     int64_t K, int64_t T, int64_t bos_index,
                                     std::vector<at::Tensor> att, int64_t cell,
-                                    std::vector<at::Tensor> state0, std::vector<at::Tensor> up) {
+                                    std::vector<at::Tensor> state0, std::vector<at::Tensor> up,
+                                    int64_t rows_per_video, double top_p, double temperature,
+                                    c10::optional<at::Tensor> rng) {
   check_cuda(wx, "wx");
   check_cuda(vgate, "vgate");
+  if (rows_per_video > 0)  // the truncated sampling decode: K is top_k
+    return sample_topk(wx, ptab, whh, wlog, blog, vgate, K, T, bos_index, att, cell, state0, up,
+                       rows_per_video, top_p, temperature, rng.has_value() ? *rng : at::Tensor());
   TORCH_CHECK(K >= 1 && K <= 16, "beam_size must be in [1, 16]");
   const int64_t H4 = wx.size(0), H = H4 / 4, V = wlog.size(0), B = vgate.size(0), R = B * K;
   TORCH_CHECK(K <= V, "beam_size > vocab_size");
-  // temporal attention: att = {Gv, P, W_q, w_a, b_a} as in decoder_forward; the
-  // query of a beam row comes from its parent's h (q rows gathered by parent)
-  const AttOperands ao = AttOperands::parse(att, Site::Beam, H, R, K, 0);
+  // the query of a beam row comes from its parent's h (q rows gathered by parent)
+  DecodeRows d(wx, ptab, whh, wlog, blog, vgate, K, K, bos_index, att, cell, state0, up);
+  const AttOperands& ao = d.ao;
   const bool has_att = ao.on;
   const int64_t C = ao.C, A = ao.A;
   const int per_frame = ao.per_frame, CPAD = ao.CPAD;
-  at::Tensor vg_rows, qb;
-  auto dev = wx.device();
-  auto f32 = at::TensorOptions().dtype(at::kFloat).device(dev);
-  auto i64 = at::TensorOptions().dtype(at::kLong).device(dev);
-  auto i32 = at::TensorOptions().dtype(at::kInt).device(dev);
-  hipStream_t st = cur_stream();
-  const int64_t ldl = (V + 7) / 8 * 8;
-  const int n_vt = vocab_num_tiles((int)V);
-  // K <= 8: the vocab launch keeps each tile's K best logits per row (VF_TOPK)
-  // and the top-K merges n_vt * K candidates -- no R x V fp32 logits
-  const bool tile_topk = K <= 8;
-  at::Tensor logits = tile_topk ? at::empty({(int64_t)n_vt * R * K * 2}, f32) : at::empty({R, ldl}, f32);
-  at::Tensor lse = at::empty({R}, f32);
-  at::Tensor part = at::empty({(int64_t)n_vt * R * vocab_partial_bytes() / 4}, f32);
+  at::Tensor& vg_rows = d.vg_rows;
+  const at::TensorOptions f32 = d.f32, i64 = d.i64, i32 = d.i32;
+  hipStream_t st = d.st;
+  const int64_t ldl = d.ldl;
+  const int n_vt = d.n_vt;
+  const bool tile_topk = d.tile_topk;
+  at::Tensor &logits = d.logits, &lse = d.lse, &part = d.part, &tok = d.tok;
   at::Tensor top_v = at::empty({R, K}, f32);
   at::Tensor top_i = at::empty({R, K}, i32);
   at::Tensor beam_sum = at::zeros({R}, f32);
@@ -47,33 +202,15 @@ std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor w
   at::Tensor best_ppl = at::full({B}, INFINITY, f32);
   at::Tensor best_seq = at::zeros({B, T}, i64);
   at::Tensor best_lp = at::zeros({B, T}, f32);
-  at::Tensor tok = at::full({R}, bos_index, i64);
   at::Tensor parent = at::empty({R}, i32);
-  // stacked layers: up = {[W_ih | W_hh] (4H, 2H), W_hh (4H, H)} per upper layer
-  const UpperLayers upl = UpperLayers::parse(up, Site::Beam, has_att, !state0.empty(), H, 0);
-  const int64_t NL = upl.NL;
-  std::vector<std::array<at::Tensor, 2>> hl(NL), cl(NL);
-  for (int64_t l = 0; l < NL; ++l) {
-    hl[l] = {at::zeros({R, H}, wx.options()), at::empty({R, H}, wx.options())};
-    cl[l] = {at::zeros({R, H}, f32), at::empty({R, H}, f32)};
-  }
-  at::Tensor xin = NL > 1 ? at::empty({R, H4}, f32) : at::Tensor();
-  at::Tensor* h = hl[0].data();
-  at::Tensor* c = cl[0].data();
-  const InitState s0 = InitState::parse(state0, Site::Beam, has_att, B, H);
-  if (s0.on) {  // per-video initial state {h0 (B, H), c0 (B, H)}, one copy per beam
-    h[0].copy_(s0.h0.repeat_interleave(K, 0));
-    c[0].copy_(s0.c0.repeat_interleave(K, 0));
-  }
+  const int64_t NL = d.NL;
+  at::Tensor* h = d.hl[0].data();
+  at::Tensor* c = d.cl[0].data();
   const uint16_t* W = reinterpret_cast<const uint16_t*>(wlog.data_ptr());
   const uint16_t* WHH = reinterpret_cast<const uint16_t*>(whh.data_ptr());
   // (MFMA attention for the beam rows -- parent-gathered query input, the
   // decode launch's attention workgroups on their own -- measured slower,
   // 26.0k vs 29.6k videos/s at att8 beam 5, profiles/r4/README_r4.md)
-  if (has_att) {
-    vg_rows = at::empty({R, H4}, f32);
-    qb = at::empty({R, A}, f32);
-  }
   // Fused form (one layer, no attention, K <= 8): per decode step TWO launches
   // -- the vocab launch (tile top-K candidates + partials) carrying the NEXT
   // step's recurrent GEMM pre = h W_hh^T + video gates for every current row,
@@ -158,44 +295,7 @@ std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor w
                        tok.data_ptr<int64_t>(), parent.data_ptr<int>(), st);
       if (t == T - 2) break;  // the reference's last LSTM step feeds nothing
     }
-    const at::Tensor& hp = h[t & 1];
-    const at::Tensor& cp = c[t & 1];
-    at::Tensor& ho = h[(t + 1) & 1];
-    at::Tensor& co = c[(t + 1) & 1];
-    if (has_att) {
-      if (t >= 1) at::mm_out(qb, hp, ao.wq.t(), at::kFloat);
-      launch_att_fwd(ao.gv.data_ptr<float>(), ao.pre.data_ptr<float>(),
-                     t >= 1 ? qb.data_ptr<float>() : nullptr, t >= 1 ? parent.data_ptr<int>() : nullptr,
-                     ao.wa.data_ptr<float>(), ao.ba.data_ptr<float>(), (int)B, (int)K, (int)C,
-                     (int)A, (int)H4, vg_rows.data_ptr<float>(), nullptr, st, 0, per_frame);
-    }
-    launch_lstm_step_fwd(tok.data_ptr<int64_t>(), 1, reinterpret_cast<const uint16_t*>(ptab.data_ptr()),
-                         reinterpret_cast<const uint16_t*>(hp.data_ptr()), cp.data_ptr<float>(),
-                         has_att ? vg_rows.data_ptr<float>() : vgate.data_ptr<float>(),
-                         has_att ? 1 : (int)K, (int)R, (int)H, WHH,
-                         reinterpret_cast<uint16_t*>(ho.data_ptr()), co.data_ptr<float>(), nullptr,
-                         (int)H, 0.f, nullptr, (int)t, nullptr, st,
-                         t >= 1 ? parent.data_ptr<int>() : nullptr, (int)cell);
-    for (int64_t l = 1; l < NL; ++l) {  // upper layers: their state follows the parent beam too
-      at::mm_out(xin, hl[l - 1][(t + 1) & 1], upl(l, 0).narrow(1, 0, H).t(), at::kFloat);
-      launch_lstm_step_fwd(nullptr, 0, nullptr,
-                           reinterpret_cast<const uint16_t*>(hl[l][t & 1].data_ptr()),
-                           cl[l][t & 1].data_ptr<float>(), xin.data_ptr<float>(), 1, (int)R,
-                           (int)H, reinterpret_cast<const uint16_t*>(upl(l, 1).data_ptr()),
-                           reinterpret_cast<uint16_t*>(hl[l][(t + 1) & 1].data_ptr()),
-                           cl[l][(t + 1) & 1].data_ptr<float>(), nullptr, (int)H, 0.f, nullptr,
-                           (int)t, nullptr, st, t >= 1 ? parent.data_ptr<int>() : nullptr,
-                           (int)cell);
-    }
-    const at::Tensor& htop = hl[NL - 1][(t + 1) & 1];
-    launch_vocab_fwd(reinterpret_cast<const uint16_t*>(htop.data_ptr()), (int)H, (int)R, (int)H, W,
-                     blog.data_ptr<float>(), (int)V,
-                     reinterpret_cast<uint16_t*>(logits.data_ptr()), ldl, part.data_ptr(),
-                     nullptr, 0, tile_topk ? (VF_TOPK_H | ((int)K << 8)) : /*fp32 logits*/ 8, 1.f,
-                     nullptr, (int)t, st);
-    launch_vocab_combine(part.data_ptr(), n_vt, (int)R, lse.data_ptr<float>(), nullptr, 0,
-                         nullptr, 0, nullptr, 0, nullptr, 0, SEL_GT_H, 0.f, nullptr, (int)t, nullptr,
-                         0, nullptr, st);
+    d.step(t, t >= 1 ? parent.data_ptr<int>() : nullptr, /*combine=*/true);
   }
   return {best_seq, best_lp};
 }

@@ -372,7 +372,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("att_bench", &cst::att_bench);
   m.def("token_sort", &cst::token_sort);
   m.def("token_group_sum", &cst::token_group_sum);
-  m.def("vocab_select", &cst::vocab_select);
+  // top_k > 0: the VF_TOPK vocab launch + topk_sample_kernel -> (tok, lse, lp)
+  m.def("vocab_select", &cst::vocab_select, py::arg("hd"), py::arg("wlog"), py::arg("blog"),
+        py::arg("rng"), py::arg("mode"), py::arg("temperature"), py::arg("step"),
+        py::arg("top_k") = 0, py::arg("top_p") = 1.0);
   m.def("decode_step_test", &cst::decode_step_test, py::arg("hd"), py::arg("h"), py::arg("wlog"),
         py::arg("blog"), py::arg("whh"), py::arg("vgate"), py::arg("vdiv"), py::arg("tgt"),
         py::arg("eoff"), py::arg("save"), py::arg("mode"), py::arg("step"), py::arg("rng"),
@@ -403,7 +406,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("reset_device_errors", &cst::reset_device_errors);
   m.def("att_mfma_fwd", &cst::att_mfma_fwd, py::arg("h"), py::arg("wq"), py::arg("P"),
         py::arg("wa"), py::arg("ba"), py::arg("gv"), py::arg("whole") = -1);
-  m.def("beam_search", &cst::beam_search);
+  // rows_per_video > 0: truncated sampling instead (K = top_k, see beam_search.cpp)
+  m.def("beam_search", &cst::beam_search, py::arg("wx"), py::arg("ptab"), py::arg("whh"),
+        py::arg("wlog"), py::arg("blog"), py::arg("vgate"), py::arg("K"), py::arg("T"),
+        py::arg("bos_index"), py::arg("att"), py::arg("cell"), py::arg("state0"), py::arg("up"),
+        py::arg("rows_per_video") = 0, py::arg("top_p") = 1.0, py::arg("temperature") = 1.0,
+        py::arg("rng") = py::none());
   // idx / C: optional int64 row index into resident feature tables (C frames per row)
   m.def("featpool_forward", &cst::featpool_forward, py::arg("xs"), py::arg("ws"), py::arg("bs"),
         py::arg("drop_p"), py::arg("rng"), py::arg("idx") = py::none(), py::arg("C") = 1);

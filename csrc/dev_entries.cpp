@@ -342,7 +342,7 @@ std::vector<at::Tensor> att_mfma_fwd(at::Tensor h, at::Tensor wq, at::Tensor P, 
 
 std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor blog,
                                      at::Tensor rng, int64_t mode, double temperature,
-                                     int64_t step) {
+                                     int64_t step, int64_t top_k, double top_p) {
   check_cuda(hd, "hd");
   check_cuda(wlog, "wlog");
   TORCH_CHECK(hd.scalar_type() == at::kBFloat16 && wlog.scalar_type() == at::kBFloat16 &&
@@ -357,6 +357,27 @@ std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor 
   at::Tensor tok = at::zeros({R, 1}, at::TensorOptions().dtype(at::kLong).device(dev));
   at::Tensor lse = at::empty({R}, at::TensorOptions().dtype(at::kFloat).device(dev));
   hipStream_t st = cur_stream();
+  if (top_k > 0) {
+    // truncated sampling (kernels/topk_sample.hip): the VF_TOPK vocab launch's
+    // tile candidates + partials -> {token, lse, log-prob of the token}
+    TORCH_CHECK(mode == SEL_SAMPLE_H, "top_k: sampling mode only");
+    TORCH_CHECK(top_k <= 8 && top_k <= V, "top_k must be in [1, min(8, V)]");
+    TORCH_CHECK(top_p > 0.0 && top_p <= 1.0 && temperature > 0.0, "top_p in (0, 1], temperature > 0");
+    at::Tensor cand = at::empty({(int64_t)n_vt * R * top_k * 2}, lse.options());
+    at::Tensor lp = at::empty({R}, lse.options());
+    launch_vocab_fwd(reinterpret_cast<const uint16_t*>(hd.data_ptr()), (int)H, (int)R, (int)H,
+                     reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(),
+                     (int)V, reinterpret_cast<uint16_t*>(cand.data_ptr()), (V + 7) / 8 * 8,
+                     part.data_ptr(), nullptr, 0, VF_TOPK_H | ((int)top_k << 8), 1.f, nullptr,
+                     (int)step, st);
+    TopkSampleArgs sa{reinterpret_cast<const VocabPartial*>(part.data_ptr()),
+                      reinterpret_cast<const float2*>(cand.data_ptr()), n_vt, (int)R, (int)top_k,
+                      (int)V, (float)top_p, (float)(1.0 / temperature), rng_ptr(rng), (int)step,
+                      nullptr, tok.data_ptr<int64_t>(), 1, nullptr, lp.data_ptr<float>(), 1,
+                      lse.data_ptr<float>()};
+    launch_topk_sample(sa, st);
+    return {tok.view({R}), lse, lp};
+  }
   launch_vocab_fwd(reinterpret_cast<const uint16_t*>(hd.data_ptr()), (int)H, (int)R, (int)H,
                    reinterpret_cast<const uint16_t*>(wlog.data_ptr()), blog.data_ptr<float>(),
                    (int)V, nullptr, 0, part.data_ptr(), nullptr, 0, mode == SEL_SAMPLE_H ? 1 : 2,

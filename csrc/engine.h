@@ -43,7 +43,10 @@ std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor w
                                     at::Tensor wlog, at::Tensor blog, at::Tensor vgate,
                                     int64_t K, int64_t T, int64_t bos_index,
                                     std::vector<at::Tensor> att, int64_t cell,
-                                    std::vector<at::Tensor> state0, std::vector<at::Tensor> up);
+                                    std::vector<at::Tensor> state0, std::vector<at::Tensor> up,
+                                    int64_t rows_per_video = 0, double top_p = 1.0,
+                                    double temperature = 1.0,
+                                    c10::optional<at::Tensor> rng = c10::nullopt);
 
 // engine.cpp: the executor's shared state
 void set_stamp_base(int64_t base);
@@ -135,7 +138,7 @@ std::vector<at::Tensor> att_mfma_fwd(at::Tensor h, at::Tensor wq, at::Tensor P, 
                                      int64_t whole);
 std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor blog,
                                      at::Tensor rng, int64_t mode, double temperature,
-                                     int64_t step);
+                                     int64_t step, int64_t top_k = 0, double top_p = 1.0);
 std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor wlog,
                                          at::Tensor blog, at::Tensor whh, at::Tensor vgate,
                                          int64_t vdiv, at::Tensor tgt, at::Tensor eoff,

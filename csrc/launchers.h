@@ -703,4 +703,23 @@ void launch_beam_step(const float* top_v, const int* top_i, int B, int K, int T,
                       int64_t* best_seq, float* best_lp, int64_t* tok_out, int* parent_out,
                       hipStream_t stream);
 
+// topk_sample.hip: one step of truncated (top-k / nucleus) sampling from the
+// vocab launch's VF_TOPK output, one wavefront per row
+struct TopkSampleArgs {
+  const struct VocabPartial* part;  // (n_vt, R) tile partials of the vocab launch
+  const float2* cand;               // (n_vt, R, K) tile candidates (VF_TOPK)
+  int n_vt, R, K, V;                // K = top_k in [1, 8]
+  float top_p, inv_tau;             // nucleus mass in (0, 1]; 1 / temperature
+  const uint32_t* rng;              // (device, nullable) int32[2] seeds, slot 1 = sampling
+  int step;                         // decode step (key of the draw)
+  uint8_t* unfinished;              // nullable (R) row mask, updated in place
+  int64_t* tok_out;                 // token of row r at tok_out[r * tok_stride]
+  int64_t tok_stride;
+  int64_t* next_tok;                // nullable (R): the next step's input token
+  float* lp_out;                    // the token's log-prob at temperature 1, row stride lp_stride
+  int64_t lp_stride;
+  float* lse_out;                   // nullable (R)
+};
+void launch_topk_sample(const TopkSampleArgs& a, hipStream_t stream);
+
 }  // namespace cst

@@ -61,6 +61,28 @@ def label_smoothing_arg(spec):
     return e
 
 
+def mbr_top_k_arg(spec):
+    """``--mbr_top_k``: an integer >= 0; 0 = no truncation."""
+    try:
+        k = int(spec)
+    except ValueError:
+        raise argparse.ArgumentTypeError('not an integer: %r' % spec)
+    if k < 0:
+        raise argparse.ArgumentTypeError('--mbr_top_k must be >= 0, got %r' % spec)
+    return k
+
+
+def mbr_top_p_arg(spec):
+    """``--mbr_top_p``: a finite float in (0, 1]; 1 = no nucleus cut."""
+    try:
+        p = float(spec)
+    except ValueError:
+        raise argparse.ArgumentTypeError('not a number: %r' % spec)
+    if not 0.0 < p <= 1.0:  # (NaN fails the comparison too)
+        raise argparse.ArgumentTypeError('--mbr_top_p must be in (0, 1], got %r' % spec)
+    return p
+
+
 RL_OBJECTIVES = ('reinforce', 'risk', 'softmax_margin', 'multi_margin')
 
 
@@ -196,6 +218,15 @@ def build_parser():
         help='--decode mbr: multinomial samples per video beside the standard caption')
     add('--mbr_temperature', type=float, default=1.0,
         help='--decode mbr: sampling temperature of those samples')
+    add('--mbr_top_k', type=mbr_top_k_arg, default=0, metavar='K',
+        help='--decode mbr: draw each word of those samples from the K most probable words '
+             'only (truncated sampling; the temperature applies inside them).  On the fused '
+             'engine K <= 8 runs in csrc/kernels/topk_sample.hip, larger K through the PyTorch '
+             'path.  0 (default): no truncation')
+    add('--mbr_top_p', type=mbr_top_p_arg, default=1.0, metavar='P',
+        help='--decode mbr: nucleus inside the --mbr_top_k words: the shortest prefix of them '
+             '(most probable first) whose renormalised mass reaches P, in (0, 1]; P < 1 needs '
+             '--mbr_top_k >= 1.  1 (default): all K words')
     add('--mbr_mix', type=mbr_mix_arg, default='', metavar='METRIC:WEIGHT[,...]',
         help='--decode mbr: the utility the captions of a pool are scored under, in the grammar '
              'of --reward_mix, e.g. CIDEr:1,Bleu_4:5,ROUGE_L:5 (peer CIDEr-D on its x10 scale, '
@@ -271,7 +302,12 @@ def build_parser():
 
 
 def parse_opts(argv=None):
-    return build_parser().parse_args(argv)
+    p = build_parser()
+    opt = p.parse_args(argv)
+    if opt.mbr_top_p < 1.0 and opt.mbr_top_k == 0:
+        p.error('--mbr_top_p < 1 needs --mbr_top_k >= 1 (the nucleus is taken inside the '
+                'top-k candidates)')
+    return opt
 
 
 def default_opts(**overrides):

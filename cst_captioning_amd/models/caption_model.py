@@ -33,6 +33,53 @@ from ..utils.text import BOS
 from .modules import FeatPool, FeatExpander, RNNUnit, MANet, TemporalAttention
 
 
+def check_truncation(top_k, top_p, vocab_size=None):
+    """The truncated sampler's arguments: ``top_k`` an integer >= 0 (0 = no
+    truncation, at most the vocabulary size), ``top_p`` finite in (0, 1], and
+    ``top_p < 1`` only with ``top_k >= 1`` (the nucleus is taken inside the
+    top-k candidates).  Returns them as ``(int, float)``; ValueError
+    otherwise."""
+    if isinstance(top_k, bool) or int(top_k) != top_k or top_k < 0:
+        raise ValueError('top_k must be an integer >= 0, got %r' % (top_k,))
+    top_k, top_p = int(top_k), float(top_p)
+    if not (math.isfinite(top_p) and 0.0 < top_p <= 1.0):
+        raise ValueError('top_p must be in (0, 1], got %r' % (top_p,))
+    if top_p < 1.0 and top_k == 0:
+        raise ValueError('top_p < 1 needs top_k >= 1 (the nucleus is taken inside the top-k '
+                         'candidates)')
+    if vocab_size is not None and top_k > vocab_size:
+        raise ValueError('top_k > vocab_size')
+    return top_k, top_p
+
+
+def truncated_probs(logprobs, top_k, top_p=1.0, temperature=1.0):
+    """The distribution one truncated sampling step draws from.  ``logprobs``
+    (n, V): log-softmax at temperature 1.  Per row: the ``top_k`` largest
+    entries (ties to the smaller index) ordered by value descending, then
+    index ascending; weights ``w_i = exp((lp_i - lp_0) / temperature)``,
+    ``q = w / sum w``; the nucleus is the shortest prefix whose mass reaches
+    ``top_p`` (all ``top_k`` candidates at ``top_p = 1``); the result is ``q``
+    renormalised over that prefix, (n, V), zero outside it.  ``top_k = 0``:
+    the plain tempered softmax."""
+    top_k, top_p = check_truncation(top_k, top_p, logprobs.size(-1))
+    temperature = float(temperature)
+    if not temperature > 0.0:
+        raise ValueError('temperature must be positive, got %r' % (temperature,))
+    lp = logprobs if logprobs.dtype in (torch.float32, torch.float64) else logprobs.float()
+    if top_k == 0:
+        return F.softmax(lp / temperature, dim=-1)
+    # (a stable descending sort keeps equal values in index order)
+    vals, idx = torch.sort(lp, dim=-1, descending=True, stable=True)
+    vals, idx = vals[..., :top_k], idx[..., :top_k]
+    w = ((vals - vals[..., :1]) / temperature).exp()
+    q = w / w.sum(-1, keepdim=True)
+    if top_p < 1.0:
+        # candidate i is kept while the mass before it is still short of top_p
+        q = q * ((q.cumsum(-1) - q) < top_p)
+        q = q / q.sum(-1, keepdim=True)
+    return torch.zeros_like(lp).scatter_(-1, idx, q)
+
+
 class CaptionModel(nn.Module):
 
     def __init__(self, opt):
@@ -179,6 +226,12 @@ class CaptionModel(nn.Module):
         beam_size = opt.get('beam_size', 1)
         if beam_size > 1:
             return self.sample_beam(feats, opt)
+        # truncated sampling (module function truncated_probs): top_k best
+        # words, the nucleus top_p inside them; greedy decoding ignores both
+        top_k, top_p = 0, 1.0
+        if opt.get('sample_max', 1) != 1:
+            top_k, top_p = check_truncation(opt.get('top_k', 0), opt.get('top_p', 1.0),
+                                            self.vocab_size)
         if self.impl == 'hip' and self._engine is not None:
             return self._engine.sample(self, feats, opt)
         sample_max = opt.get('sample_max', 1)
@@ -202,8 +255,11 @@ class CaptionModel(nn.Module):
                 elif sample_max == 1:
                     lp_t, it = torch.max(logprobs.detach(), 1)
                 else:
-                    p = (logprobs.detach() / temperature).exp() if temperature != 1.0 \
-                        else logprobs.detach().exp()
+                    if top_k > 0:
+                        p = truncated_probs(logprobs.detach(), top_k, top_p, temperature)
+                    else:
+                        p = (logprobs.detach() / temperature).exp() if temperature != 1.0 \
+                            else logprobs.detach().exp()
                     it = torch.multinomial(p, 1).view(-1)
                     lp_t = logprobs.gather(1, it.unsqueeze(1)).view(-1)
                 xt = self.embed(it)
@@ -224,8 +280,10 @@ class CaptionModel(nn.Module):
         """The caption that agrees most with what the model itself says about
         the video.  The pool of video ``k``: row 0 the standard decode (greedy
         for ``beam_size`` 1, else beam search), rows 1..N multinomial samples
-        (``N = opt['mbr_samples']``, ``opt['mbr_temperature']``, one expanded
-        call), all padded with 0 to one width; ``G = N + 1``.  Every row is
+        (``N = opt['mbr_samples']``, ``opt['mbr_temperature']``, truncated to
+        the ``opt['mbr_top_k']`` best words and the nucleus ``opt['mbr_top_p']``
+        inside them when ``mbr_top_k >= 1``, one expanded call), all padded
+        with 0 to one width; ``G = N + 1``.  Every row is
         scored against its peers by ``opt['mbr_scorer']``
         (:class:`..ops.mbr.PeerCiderD`, or :class:`..ops.mbr.PeerMix` for a
         mixed utility) and the best row is returned, index 0
@@ -243,13 +301,19 @@ class CaptionModel(nn.Module):
             raise ValueError('mbr_samples must be at least 1, got %d' % N)
         std = {k: v for k, v in opt.items() if not k.startswith('mbr_') and k != 'decode'}
         std.update(sample_max=1, expand_feat=0)
+        sampled = {'sample_max': 0, 'expand_feat': 1, 'beam_size': 1,
+                   'temperature': float(opt.get('mbr_temperature', 1.0))}
+        # truncated sampling of rows 1..N only (absent or 0 / 1.0: the keys are
+        # not passed, the plain sampler's call as before)
+        top_k, top_p = check_truncation(opt.get('mbr_top_k', 0), opt.get('mbr_top_p', 1.0),
+                                        self.vocab_size)
+        if top_k > 0:
+            sampled.update(top_k=top_k, top_p=top_p)
         seq0, lp0 = self.sample(feats, std)
         prev = self.seq_per_img
         self.set_seq_per_img(N)
         try:
-            seqs, lps = self.sample(feats, {'sample_max': 0, 'expand_feat': 1, 'beam_size': 1,
-                                            'temperature': float(opt.get('mbr_temperature',
-                                                                         1.0))})
+            seqs, lps = self.sample(feats, sampled)
         finally:
             self.set_seq_per_img(prev)
         B, G = seq0.size(0), N + 1

@@ -72,6 +72,7 @@ Supported configuration: ``rnn_type lstm | gru | rnn``, ``model_type concat
 ``concat``, ``num_layers >= 1`` (> 1 with concat, no attention); other
 configurations use the PyTorch path (``build_model`` decides).
 """
+import logging
 import os
 
 import torch
@@ -80,6 +81,8 @@ import torch.nn.functional as F
 from .. import _ext
 from ..utils.consts import const_tensor
 from ..utils.text import BOS
+
+logger = logging.getLogger(__name__)
 
 SEL_GT, SEL_SAMPLE, SEL_GREEDY, SEL_SS = 0, 1, 2, 3
 # teacher-forced training forwards on the XE decode launches (csrc/decoder_forward.cpp
@@ -952,6 +955,13 @@ class DecoderEngine:
         sample_max = opt.get('sample_max', 1)
         temperature = opt.get('temperature', 1.0)
         expand = opt.get('expand_feat', 0) == 1
+        if sample_max != 1:
+            from .caption_model import check_truncation
+            top_k, top_p = check_truncation(opt.get('top_k', 0), opt.get('top_p', 1.0),
+                                            model.vocab_size)
+            if top_k > 0:
+                return self._sample_topk(model, feats, opt, top_k, top_p, float(temperature),
+                                         expand)
         T = model.seq_length - 1
         modes = [SEL_GREEDY if sample_max == 1 else SEL_SAMPLE] * (T - 1)
         # (temporal attention, one greedy row per video: decoding each video on
@@ -964,6 +974,32 @@ class DecoderEngine:
                                   temperature=temperature)
         return seq, lp
 
+    def _sample_topk(self, model, feats, opt, top_k, top_p, temperature, expand):
+        """Truncated sampling (``caption_model.truncated_probs``) on the GPU:
+        per step the cell, the vocab launch's per-tile ``top_k`` candidates
+        and ``csrc/kernels/topk_sample.hip`` (``beam_search.cpp`` sample_topk).
+        The tile candidates hold at most 8 per tile, so ``top_k > 8`` decodes
+        through the PyTorch loop, as ``sample_beam`` does for beams over 16."""
+        if top_k > 8:
+            if not getattr(self, '_warned_topk', False):
+                self._warned_topk = True
+                logger.warning('top_k = %d > 8: truncated sampling decodes through the PyTorch '
+                               'path (the fused engine serves top_k <= 8)', top_k)
+            model.impl = 'torch'
+            try:
+                return model.sample(feats, opt)
+            finally:
+                model.impl = 'hip'
+        if not temperature > 0.0:
+            raise ValueError('temperature must be positive, got %r' % (temperature,))
+        vg, blog, att, state0 = self._decode_operands(model, feats)
+        S = model.feat_expander.n if expand else 1
+        seq, lp = _ext.ops().beam_search(self.wx, self.ptab, self.whh, self.wlog, blog, vg, top_k,
+                                         model.seq_length, BOS, att, self.cell, state0,
+                                         self.upper_operands(), S, top_p, temperature,
+                                         self._rng(vg.device))
+        return seq, lp
+
     def _att_mfma_shape_ok(self, model):
         """The MFMA attention's shape limits (csrc/kernels/vocab.hip
         att_mfma_ok, shared scorer): frames <= 16, A % 64 == 0 and <= 1024,
@@ -972,18 +1008,11 @@ class DecoderEngine:
         A, H = self.att_dim, self.H
         return 1 <= C <= 16 and A % 64 == 0 and A <= 1024 and H % 32 == 0 and 64 <= H <= 512
 
-    @torch.no_grad()
-    def sample_beam(self, model, feats, opt):
-        """Batched on-GPU beam search (``csrc/kernels/beam.hip``) with the
-        reference's selection / harvesting / perplexity-ranking semantics
-        (``model.py:369-512``)."""
-        K = opt.get('beam_size', 5)
-        if K > 16:
-            model.impl = 'torch'
-            try:
-                return model.sample_beam(feats, opt)
-            finally:
-                model.impl = 'hip'
+    def _decode_operands(self, model, feats):
+        """Per-video operands of the native decode loops (``beam_search.cpp``):
+        video gates (B, 4H) fp32, the fp32 logit bias, the attention list
+        {Gv, P, W_q, w_a, b_a} (or []) and the initial state {h0, c0} of
+        'standard' (or [])."""
         att = []
         if self.attention:
             (gv, pre, _, wa, ba), _ = self._att_inputs(model, feats)
@@ -999,6 +1028,21 @@ class DecoderEngine:
         self.ensure_ptab()
         blog = model.logit.bias.detach().float().contiguous()
         vg = vg.detach().float().contiguous()
+        return vg, blog, att, state0
+
+    @torch.no_grad()
+    def sample_beam(self, model, feats, opt):
+        """Batched on-GPU beam search (``csrc/kernels/beam.hip``) with the
+        reference's selection / harvesting / perplexity-ranking semantics
+        (``model.py:369-512``)."""
+        K = opt.get('beam_size', 5)
+        if K > 16:
+            model.impl = 'torch'
+            try:
+                return model.sample_beam(feats, opt)
+            finally:
+                model.impl = 'hip'
+        vg, blog, att, state0 = self._decode_operands(model, feats)
         if (not state0 and self.layers == 1 and vg.is_cuda
                 and os.environ.get('CSTCAP_BEAM_GRAPH', '1') != '0'
                 and not torch.cuda.is_current_stream_capturing()):

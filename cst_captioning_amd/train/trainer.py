@@ -962,6 +962,11 @@ class Trainer:
             raise ValueError('--mbr_samples must be at least 1, got %d' % opt.mbr_samples)
         if not float(opt.mbr_temperature) > 0:
             raise ValueError('--mbr_temperature must be positive, got %r' % opt.mbr_temperature)
+        from ..models.caption_model import check_truncation
+        try:
+            check_truncation(getattr(opt, 'mbr_top_k', 0), getattr(opt, 'mbr_top_p', 1.0))
+        except ValueError as e:
+            raise ValueError('--mbr_top_k / --mbr_top_p: %s' % e)
         from ..ops.mbr import PeerCiderD, PeerMix
         if weights is not None:
             return PeerMix(df if weights[0] else None, weights, use_eos=opt.use_eos,
@@ -975,6 +980,8 @@ class Trainer:
         if self.mbr_scorer is not None:
             o.update(decode='mbr', mbr_samples=int(self.opt.mbr_samples),
                      mbr_temperature=float(self.opt.mbr_temperature),
+                     mbr_top_k=int(getattr(self.opt, 'mbr_top_k', 0)),
+                     mbr_top_p=float(getattr(self.opt, 'mbr_top_p', 1.0)),
                      mbr_scorer=self.mbr_scorer)
         return o
 

@@ -4,7 +4,11 @@ the fused engine: mean validation CIDEr-D (the reward kernel against the
 validation split's references, train-split document frequencies, x10) of the
 captions each decoder returns.  Information only: a synthetic task.
 
-usage: python scripts/mbr_quality.py [XE_STEPS] [MBR_SAMPLES]
+usage: python scripts/mbr_quality.py [XE_STEPS] [MBR_SAMPLES] [TOP_K] [TOP_P]
+
+TOP_K >= 1 adds, beside every consensus row, the same decode with its samples
+truncated to the TOP_K most probable words and the nucleus TOP_P inside them
+(``--mbr_top_k`` / ``--mbr_top_p``; default 0 / 1.0: not run).
 
 Prints one JSON line.
 """
@@ -25,6 +29,8 @@ from cst_captioning_amd.train.trainer import Trainer  # noqa: E402
 
 xe_steps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+top_k = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+top_p = float(sys.argv[4]) if len(sys.argv) > 4 else 1.0
 if not torch.cuda.is_available():
     sys.exit('needs a GPU')
 dev = torch.device('cuda', 0)
@@ -68,7 +74,7 @@ def val_cider(o):
 
 
 res = {'xe_steps': xe_steps, 'xe_loss': round(float(out['loss']), 4), 'videos': va.num_videos,
-       'mbr_samples': N}
+       'mbr_samples': N, 'top_k': top_k, 'top_p': top_p}
 res['greedy'] = val_cider({'beam_size': 1})[0]
 res['beam5'] = val_cider({'beam_size': 5})[0]
 for bs in (1, 5):
@@ -76,6 +82,12 @@ for bs in (1, 5):
         torch.manual_seed(1)
         c, moved, n = val_cider({'decode': 'mbr', 'beam_size': bs, 'mbr_samples': N,
                                  'mbr_temperature': temp, 'mbr_scorer': peer})
-        res['mbr_row0_%s_t%.1f' % ('greedy' if bs == 1 else 'beam5', temp)] = {
-            'cider_d': c, 'not_row0': moved, 'of': n}
+        key = 'mbr_row0_%s_t%.1f' % ('greedy' if bs == 1 else 'beam5', temp)
+        res[key] = {'cider_d': c, 'not_row0': moved, 'of': n}
+        if top_k > 0:  # the same pools' seed, the samples truncated
+            torch.manual_seed(1)
+            c, moved, n = val_cider({'decode': 'mbr', 'beam_size': bs, 'mbr_samples': N,
+                                     'mbr_temperature': temp, 'mbr_top_k': top_k,
+                                     'mbr_top_p': top_p, 'mbr_scorer': peer})
+            res[key + '_top%d_p%.2f' % (top_k, top_p)] = {'cider_d': c, 'not_row0': moved, 'of': n}
 print(json.dumps(res))
