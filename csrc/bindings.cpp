@@ -456,4 +456,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ls_mode") = 0, py::arg("ls_eps") = 0.0, py::arg("ls_dg") = py::none(),
         py::arg("ls_dw") = py::none(), py::arg("ls_db") = py::none());
   m.def("video_gate_grad", &cst::video_gate_grad);
+  // the reverse recurrence's kernels one by one (tests); None / empty tensors = not given
+  m.def("lstm_step_bwd_test", &cst::lstm_step_bwd_test, py::arg("dg_next"), py::arg("whhT"),
+        py::arg("dh_logit"), py::arg("dc_carry"), py::arg("gates"), py::arg("c_t"),
+        py::arg("c_prev"), py::arg("drop_p"), py::arg("rng"), py::arg("step"), py::arg("cell"),
+        py::arg("KD"), py::arg("sentinel"), py::arg("dh_scale") = py::none(),
+        py::arg("oh_W") = py::none(), py::arg("oh_a") = py::none(), py::arg("oh_ys") = py::none(),
+        py::arg("oh_b") = py::none(), py::arg("oh_yx") = py::none(),
+        py::arg("gvb16") = py::none(), py::arg("vdiv") = 1, py::arg("C") = 0);
+  m.def("lstm_bwd_loop_test", &cst::lstm_bwd_loop_test, py::arg("whhT"), py::arg("dh"),
+        py::arg("gates"), py::arg("c_all"), py::arg("drop_p"), py::arg("rng"), py::arg("cell"),
+        py::arg("form"), py::arg("scale") = py::none(), py::arg("oh_W") = py::none(),
+        py::arg("oh_a") = py::none(), py::arg("oh_ys") = py::none(), py::arg("oh_b") = py::none(),
+        py::arg("oh_yx") = py::none());
 }

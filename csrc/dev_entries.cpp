@@ -62,6 +62,208 @@ double lstm_bwd_loop_bench(int64_t R, int64_t H, int64_t T, int64_t iters, at::T
   return ms * 1e3 / std::max<int64_t>(iters, 1);
 }
 
+// the reverse recurrence's kernels one by one (tests/test_gpu_lstm_bwd.py);
+// absent optional operands: nullopt or an empty tensor
+static bool given(const c10::optional<at::Tensor>& t) {
+  return t.has_value() && t->defined() && t->numel() > 0;
+}
+static bool f32_rows(const at::Tensor& t, int64_t n) {
+  return t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.numel() == n;
+}
+static bool i32_rows(const at::Tensor& t, int64_t n) {
+  return t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous() && t.numel() == n;
+}
+// one-hot operands of NR rows -> DhOneHot (all null when W is absent); the
+// tokens of a given weight vector are required and stay below the rows of W
+static DhOneHot onehot_operands(const char* who, int64_t NR, int64_t H,
+                                const c10::optional<at::Tensor>& W,
+                                const c10::optional<at::Tensor>& a,
+                                const c10::optional<at::Tensor>& ys,
+                                const c10::optional<at::Tensor>& b,
+                                const c10::optional<at::Tensor>& yx) {
+  DhOneHot oh{};
+  if (!given(W)) {
+    TORCH_CHECK(!given(a) && !given(b) && !given(ys) && !given(yx), who,
+                ": one-hot weights / tokens without oh_W");
+    return oh;
+  }
+  TORCH_CHECK(W->is_cuda() && W->scalar_type() == at::kBFloat16 && W->dim() == 2 &&
+                  W->is_contiguous() && W->size(1) == H && W->size(0) > 0,
+              who, ": oh_W (V, H) bf16");
+  TORCH_CHECK(given(a) || given(b), who, ": oh_W without oh_a / oh_b");
+  TORCH_CHECK(given(a) == given(ys) && given(b) == given(yx), who,
+              ": oh_a with oh_ys, oh_b with oh_yx");
+  oh.W = reinterpret_cast<const uint16_t*>(W->data_ptr());
+  if (given(a)) {
+    TORCH_CHECK(f32_rows(*a, NR) && i32_rows(*ys, NR) && ys->max().item<int>() < W->size(0), who,
+                ": oh_a fp32 / oh_ys int32 (rows), tokens < V");
+    oh.a = a->data_ptr<float>();
+    oh.ys = ys->data_ptr<int>();
+  }
+  if (given(b)) {
+    TORCH_CHECK(f32_rows(*b, NR) && i32_rows(*yx, NR) && yx->max().item<int>() < W->size(0), who,
+                ": oh_b fp32 / oh_yx int32 (rows), tokens < V");
+    oh.b = b->data_ptr<float>();
+    oh.yx = yx->data_ptr<int>();
+  }
+  return oh;
+}
+
+// ONE launch_lstm_step_bwd on the caller's operands: dg_next (R, KD) bf16 or
+// empty (last step: no GEMM), whhT (H, KD) bf16, dh_logit / dc_carry / c_t
+// (R, H) fp32, c_prev (R, H) or empty (= 0), gates (R, 4H) bf16 packed 4u + g,
+// rng int32 (2); dh_scale (R); one-hot operands (DhOneHot) of the R rows;
+// gvb16 (Bv, H, CP, 4) bf16 with vdiv and C: the non-fused attention epilogue
+// (AttBwdEpi without flags).  dG (R, KD) is pre-filled with the 16-bit pattern
+// `sentinel` (the kernel owes columns [0, 4H) only); the carry is updated on a
+// clone.  Returns {dG, dc_carry, dal_part (H / 64, R, CP) or empty}.
+std::vector<at::Tensor> lstm_step_bwd_test(
+    at::Tensor dg_next, at::Tensor whhT, at::Tensor dh_logit, at::Tensor dc_carry,
+    at::Tensor gates, at::Tensor c_t, at::Tensor c_prev, double drop_p, at::Tensor rng,
+    int64_t step, int64_t cell, int64_t KD, int64_t sentinel,
+    c10::optional<at::Tensor> dh_scale, c10::optional<at::Tensor> oh_W,
+    c10::optional<at::Tensor> oh_a, c10::optional<at::Tensor> oh_ys,
+    c10::optional<at::Tensor> oh_b, c10::optional<at::Tensor> oh_yx,
+    c10::optional<at::Tensor> gvb16, int64_t vdiv, int64_t C) {
+  check_cuda(whhT, "whhT");
+  check_cuda(dh_logit, "dh_logit");
+  check_cuda(dc_carry, "dc_carry");
+  check_cuda(gates, "gates");
+  check_cuda(c_t, "c_t");
+  TORCH_CHECK(dh_logit.scalar_type() == at::kFloat && dh_logit.dim() == 2 &&
+                  dh_logit.size(0) > 0 && dh_logit.size(1) > 0 && dh_logit.size(1) % 64 == 0,
+              "lstm_step_bwd_test: dh_logit (R, H) fp32, H a multiple of 64");
+  const int64_t R = dh_logit.size(0), H = dh_logit.size(1);
+  TORCH_CHECK(KD % 64 == 0 && KD >= 4 * H && R * KD * 2 < (1LL << 31) && H * KD * 2 < (1LL << 31),
+              "lstm_step_bwd_test: KD a multiple of 64, >= 4H, operands below 2 GB");
+  TORCH_CHECK(whhT.scalar_type() == at::kBFloat16 && whhT.dim() == 2 && whhT.size(0) == H &&
+                  whhT.size(1) == KD,
+              "lstm_step_bwd_test: whhT (H, KD) bf16");
+  TORCH_CHECK(f32_rows(dc_carry, R * H) && f32_rows(c_t, R * H) &&
+                  gates.scalar_type() == at::kBFloat16 && gates.dim() == 2 && gates.size(0) == R &&
+                  gates.size(1) == 4 * H,
+              "lstm_step_bwd_test: dc_carry / c_t (R, H) fp32, gates (R, 4H) bf16");
+  const bool has_next = dg_next.defined() && dg_next.numel() > 0;
+  if (has_next)
+    TORCH_CHECK(dg_next.is_cuda() && dg_next.is_contiguous() &&
+                    dg_next.scalar_type() == at::kBFloat16 && dg_next.dim() == 2 &&
+                    dg_next.size(0) == R && dg_next.size(1) == KD,
+                "lstm_step_bwd_test: dg_next (R, KD) bf16");
+  const bool has_cp = c_prev.defined() && c_prev.numel() > 0;
+  if (has_cp) TORCH_CHECK(f32_rows(c_prev, R * H), "lstm_step_bwd_test: c_prev (R, H) fp32");
+  TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0 && cell >= 0 && cell <= 2 &&
+                  step >= 0 && step < (1LL << 31) && sentinel >= 0 && sentinel <= 0xffff,
+              "lstm_step_bwd_test: drop_p in [0, 1), cell 0..2, step >= 0, 16-bit sentinel");
+  TORCH_CHECK(rng.defined() && rng.numel() == 2, "lstm_step_bwd_test: rng int32 (2)");
+  if (given(dh_scale)) TORCH_CHECK(f32_rows(*dh_scale, R), "lstm_step_bwd_test: dh_scale (R) fp32");
+  const DhOneHot oh = onehot_operands("lstm_step_bwd_test", R, H, oh_W, oh_a, oh_ys, oh_b, oh_yx);
+  at::Tensor dG = at::empty({R, KD}, gates.options());
+  dG.view(at::kShort).fill_((int64_t)(int16_t)(uint16_t)sentinel);
+  at::Tensor carry = dc_carry.clone();
+  at::Tensor dal;
+  AttBwdEpi att{};
+  const bool has_att = given(gvb16);
+  if (has_att) {
+    const int64_t CP = C <= 8 ? 8 : 16;
+    TORCH_CHECK(C >= 1 && vdiv >= 1 && (KD / 64) % 2 == 0 &&
+                    att_bwd_epi_ok((int)vdiv, (int)C, (int)H),
+                "lstm_step_bwd_test: attention epilogue shape not supported");
+    TORCH_CHECK(gvb16->is_cuda() && gvb16->is_contiguous() &&
+                    gvb16->scalar_type() == at::kBFloat16 && gvb16->dim() == 4 &&
+                    gvb16->size(0) * vdiv >= R && gvb16->size(1) == H && gvb16->size(2) == CP &&
+                    gvb16->size(3) == 4,
+                "lstm_step_bwd_test: gvb16 (Bv >= R / vdiv, H, CP, 4) bf16");
+    dal = at::full({H / 64, R, CP}, std::nanf(""), dh_logit.options());
+    att.gvb16 = reinterpret_cast<const uint16_t*>(gvb16->data_ptr());
+    att.vdiv = (int)vdiv;
+    att.C = (int)C;
+    att.CP = (int)CP;
+    att.dal_part = dal.data_ptr<float>();
+  } else {
+    dal = at::empty({0}, dh_logit.options());
+  }
+  launch_lstm_step_bwd(has_next ? reinterpret_cast<const uint16_t*>(dg_next.data_ptr()) : nullptr,
+                       reinterpret_cast<const uint16_t*>(whhT.data_ptr()),
+                       dh_logit.data_ptr<float>(), carry.data_ptr<float>(),
+                       reinterpret_cast<const uint16_t*>(gates.data_ptr()), c_t.data_ptr<float>(),
+                       has_cp ? c_prev.data_ptr<float>() : nullptr, (int)R, (int)H, (float)drop_p,
+                       rng_ptr(rng), (int)step, reinterpret_cast<uint16_t*>(dG.data_ptr()), (int)KD,
+                       cur_stream(), (int)cell,
+                       given(dh_scale) ? dh_scale->data_ptr<float>() : nullptr,
+                       has_att ? &att : nullptr, oh.W != nullptr ? &oh : nullptr);
+  return {dG, carry, dal};
+}
+
+// ONE launch_lstm_bwd_loop (the fold kernel ahead of it when scale / one-hot
+// operands are given): whhT (H, 4H) bf16, dh (T, R, H) fp32 (cloned: the fold
+// works in place), gates (T, R, 4H) bf16, c_all (T, R, H) fp32, scale (T, R),
+// one-hot operands of all T R rows; form 1 = row-read, 0 = K-split.  Counters,
+// exchange slabs, error word and poll bound as the executor takes them.
+// Returns {dG (T, R, 4H) bf16, dc_out (R, H), dh as the loop read it}.
+std::vector<at::Tensor> lstm_bwd_loop_test(
+    at::Tensor whhT, at::Tensor dh, at::Tensor gates, at::Tensor c_all, double drop_p,
+    at::Tensor rng, int64_t cell, int64_t form, c10::optional<at::Tensor> scale,
+    c10::optional<at::Tensor> oh_W, c10::optional<at::Tensor> oh_a,
+    c10::optional<at::Tensor> oh_ys, c10::optional<at::Tensor> oh_b,
+    c10::optional<at::Tensor> oh_yx) {
+  check_cuda(whhT, "whhT");
+  check_cuda(dh, "dh");
+  check_cuda(gates, "gates");
+  check_cuda(c_all, "c_all");
+  TORCH_CHECK(dh.scalar_type() == at::kFloat && dh.dim() == 3 && dh.numel() > 0,
+              "lstm_bwd_loop_test: dh (T, R, H) fp32");
+  const int64_t T = dh.size(0), R = dh.size(1), H = dh.size(2);
+  TORCH_CHECK(T < (1 << 20) && R < (1 << 20) && H <= 512 &&
+                  lstm_bwd_loop_ok((int)R, (int)H, (int)T),
+              "lstm_bwd_loop_test: unsupported shape");
+  TORCH_CHECK(whhT.scalar_type() == at::kBFloat16 && whhT.dim() == 2 && whhT.size(0) == H &&
+                  whhT.size(1) == 4 * H,
+              "lstm_bwd_loop_test: whhT (H, 4H) bf16");
+  TORCH_CHECK(gates.scalar_type() == at::kBFloat16 && gates.dim() == 3 && gates.size(0) == T &&
+                  gates.size(1) == R && gates.size(2) == 4 * H && f32_rows(c_all, T * R * H) &&
+                  c_all.dim() == 3,
+              "lstm_bwd_loop_test: gates (T, R, 4H) bf16, c_all (T, R, H) fp32");
+  TORCH_CHECK(drop_p >= 0.0 && drop_p < 1.0 && cell >= 0 && cell <= 2 &&
+                  (form == 0 || form == 1),
+              "lstm_bwd_loop_test: drop_p in [0, 1), cell 0..2, form 0 / 1");
+  TORCH_CHECK(rng.defined() && rng.numel() == 2, "lstm_bwd_loop_test: rng int32 (2)");
+  if (given(scale)) TORCH_CHECK(f32_rows(*scale, T * R), "lstm_bwd_loop_test: scale (T, R) fp32");
+  const DhOneHot oh = onehot_operands("lstm_bwd_loop_test", T * R, H, oh_W, oh_a, oh_ys, oh_b, oh_yx);
+  // (the launcher folds when scale or oh_a is given: oh_b rides on oh_a)
+  TORCH_CHECK(oh.b == nullptr || oh.a != nullptr, "lstm_bwd_loop_test: oh_b needs oh_a");
+  const int dev = dh.device().index();
+  at::Tensor dG = at::empty({T, R, 4 * H}, gates.options());
+  dG.view(at::kShort).fill_(-1);  // (a NaN pattern: the loop owes every element)
+  at::Tensor dc = at::full({R, H}, std::nanf(""), dh.options());
+  at::Tensor dhf = dh.clone();
+  BwdLoopArgs la{};
+  la.dG = reinterpret_cast<uint16_t*>(dG.data_ptr());
+  la.whhT = reinterpret_cast<const uint16_t*>(whhT.data_ptr());
+  la.dh = dhf.data_ptr<float>();
+  la.scale = given(scale) ? scale->data_ptr<float>() : nullptr;
+  la.oh_W = oh.W;
+  la.oh_a = oh.a;
+  la.oh_ys = oh.ys;
+  la.oh_b = oh.b;
+  la.oh_yx = oh.yx;
+  la.gates = reinterpret_cast<const uint16_t*>(gates.data_ptr());
+  la.c_all = c_all.data_ptr<float>();
+  la.dc_out = dc.data_ptr<float>();
+  la.R = (int)R;
+  la.H = (int)H;
+  la.T = (int)T;
+  la.cell = (int)cell;
+  la.drop_p = (float)drop_p;
+  la.rng = rng_ptr(rng);
+  la.cnt = loop_counters(dev, lstm_bwd_loop_counter_ints((int)R, (int)H));
+  la.err = device_err_word(dev);
+  la.poll_bound = poll_bound();
+  la.form = (int)form;
+  if (la.form == 0) la.xb = loop_xb(dev, lstm_bwd_loop_xb_floats((int)R, (int)H));
+  launch_lstm_bwd_loop(la, cur_stream());
+  return {dG, dc, dhf};
+}
+
 // test entry: C (M x N) fp32 = A[:K]^T B[:K]
 at::Tensor wgrad_tn(at::Tensor A, at::Tensor B, int64_t M, int64_t N, int64_t K) {
   check_cuda(A, "A");

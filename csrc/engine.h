@@ -126,6 +126,20 @@ void refresh_shadows(at::Tensor p, at::Tensor shadow_meta, std::vector<at::Tenso
 // dev_entries.cpp: test and microbenchmark entries
 double lstm_bwd_loop_bench(int64_t R, int64_t H, int64_t T, int64_t iters, at::Tensor phases,
                            int64_t dbg);
+std::vector<at::Tensor> lstm_step_bwd_test(
+    at::Tensor dg_next, at::Tensor whhT, at::Tensor dh_logit, at::Tensor dc_carry,
+    at::Tensor gates, at::Tensor c_t, at::Tensor c_prev, double drop_p, at::Tensor rng,
+    int64_t step, int64_t cell, int64_t KD, int64_t sentinel,
+    c10::optional<at::Tensor> dh_scale, c10::optional<at::Tensor> oh_W,
+    c10::optional<at::Tensor> oh_a, c10::optional<at::Tensor> oh_ys,
+    c10::optional<at::Tensor> oh_b, c10::optional<at::Tensor> oh_yx,
+    c10::optional<at::Tensor> gvb16, int64_t vdiv, int64_t C);
+std::vector<at::Tensor> lstm_bwd_loop_test(
+    at::Tensor whhT, at::Tensor dh, at::Tensor gates, at::Tensor c_all, double drop_p,
+    at::Tensor rng, int64_t cell, int64_t form, c10::optional<at::Tensor> scale,
+    c10::optional<at::Tensor> oh_W, c10::optional<at::Tensor> oh_a,
+    c10::optional<at::Tensor> oh_ys, c10::optional<at::Tensor> oh_b,
+    c10::optional<at::Tensor> oh_yx);
 double vocab_fwd_bench(at::Tensor hd, at::Tensor wlog, at::Tensor blog, at::Tensor tgt,
                        int64_t flags, bool save, int64_t iters, int64_t variant);
 double vgrad_colsum_bench(at::Tensor E, at::Tensor alpha, int64_t V, int64_t iters);

@@ -17,7 +17,8 @@ engine's bf16-rounded weights with the engine's dropout masks."""
 import pytest
 import torch
 
-from test_gpu_headline import dropout_keep_mask, _grad_errors
+from lstm_bwd_cases import keep_mask
+from test_gpu_headline import _grad_errors
 
 pytestmark = pytest.mark.gpu
 
@@ -107,7 +108,7 @@ def _reference_att_logprobs(model, feats, tokens_in, targets, seed, drop, S):
         h = torch.sigmoid(o) * torch.tanh(c)
         hd = h
         if drop > 0:
-            hd = h * dropout_keep_mask(seed, t, R, H, drop) / (1.0 - drop)
+            hd = h * keep_mask(seed, t, R, H, drop, DEV) / (1.0 - drop)
         lp = torch.log_softmax(hd @ w['logit.weight'].t() + w['logit.bias'], -1)
         out.append(lp.gather(1, targets[:, t:t + 1]).squeeze(1))
     return torch.stack(out, 1), w

@@ -12,34 +12,11 @@ import numpy as np
 import pytest
 import torch
 
+from lstm_bwd_cases import keep_mask
+
 pytestmark = pytest.mark.gpu
 
 DEV = 'cuda'
-M32 = 0xFFFFFFFF
-
-
-def _mul32(h, c):
-    """(h * c) mod 2^32 for int64 tensors holding uint32 values."""
-    lo, hi = h & 0xFFFF, h >> 16
-    return (lo * c + (((hi * c) & 0xFFFF) << 16)) & M32
-
-
-def _mix32(h):
-    h = h ^ (h >> 16)
-    h = _mul32(h, 0x85EBCA6B)
-    h = h ^ (h >> 13)
-    h = _mul32(h, 0xC2B2AE35)
-    return h ^ (h >> 16)
-
-
-def dropout_keep_mask(seed, step, R, H, p, device=DEV):
-    """(R, H) bool keep-mask of csrc/common.h dropout_keep(seed, step, r, u, p)."""
-    r = torch.arange(R, device=device, dtype=torch.int64)[:, None]
-    u = torch.arange(H, device=device, dtype=torch.int64)[None, :]
-    h1 = _mix32((seed ^ ((step * 0x9E3779B1) & M32)) ^ _mul32(r, 0x7FEB352D))
-    h = _mix32(h1 ^ _mul32(u, 0x846CA68B))
-    u01 = ((h >> 8) + 1).float() * (1.0 / 16777216.0)
-    return u01 > p
 
 
 def _headline_model(seed=0, drop=0.5):
@@ -80,7 +57,7 @@ def _reference_logprobs(model, feats, tokens_in, targets, seed, drop, S):
         h = torch.sigmoid(o) * torch.tanh(c)
         hd = h
         if drop > 0:
-            hd = h * dropout_keep_mask(seed, t, R, H, drop) / (1.0 - drop)
+            hd = h * keep_mask(seed, t, R, H, drop, DEV) / (1.0 - drop)
         lp = torch.log_softmax(hd @ w['logit.weight'].t() + w['logit.bias'], -1)
         out.append(lp.gather(1, targets[:, t:t + 1]).squeeze(1))
     return torch.stack(out, 1), w
