@@ -88,6 +88,11 @@ MBR_TOP_P?=1.0
 # the utility of consensus decoding in the grammar of REWARD_MIX, e.g.
 # MBR_MIX=CIDEr:1,Bleu_4:5,ROUGE_L:5 (empty: CIDEr-D); passed only when set
 MBR_MIX?=
+# ensemble decoding at test time: ENSEMBLE_FILES = further checkpoints decoded
+# together with the tested one (their word probabilities averaged every step),
+# ENSEMBLE_WEIGHTS = one weight per member, the tested model first (empty: uniform)
+ENSEMBLE_FILES?=
+ENSEMBLE_WEIGHTS?=
 # EMA of the parameters kept by the fused Adam pass; validation, the best score
 # and the best checkpoint then use the averaged weights (0 = off)
 EMA_DECAY?=0
@@ -214,7 +219,9 @@ TEST_OPT=--beam_size $(BEAM_SIZE) --language_eval $(VAL_LANG_EVAL) --test_seq_pe
 	--test_batch_size $(BATCH_SIZE) --loglevel $(LOGLEVEL) --result_file $@ \
 	--decode $(DECODE) --mbr_samples $(MBR_SAMPLES) --mbr_temperature $(MBR_TEMPERATURE) \
 	--mbr_top_k $(MBR_TOP_K) --mbr_top_p $(MBR_TOP_P) \
-	$(MBR_TEST_OPT) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX))
+	$(MBR_TEST_OPT) $(if $(MBR_MIX),--mbr_mix $(MBR_MIX)) \
+	$(if $(ENSEMBLE_FILES),--ensemble_files $(ENSEMBLE_FILES)) \
+	$(if $(ENSEMBLE_WEIGHTS),--ensemble_weights $(ENSEMBLE_WEIGHTS))
 
 train: $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth
 $(MODEL_DIR)/$(EXP_NAME)/$(subst $(space),$(noop),$(FEATS))_$(TRAIN_ID).pth: \

@@ -31,14 +31,15 @@ struct DecodeRows {
              const at::Tensor& wlog_, const at::Tensor& blog_, const at::Tensor& vgate_,
              int64_t rows_, int64_t ktop_, int64_t bos_index, const std::vector<at::Tensor>& att,
              int64_t cell_, const std::vector<at::Tensor>& state0,
-             const std::vector<at::Tensor>& up)
+             const std::vector<at::Tensor>& up, int dense = -1,
+             const at::Tensor* shared_tok = nullptr)
       : wx(wx_), ptab(ptab_), whh(whh_), wlog(wlog_), blog(blog_), vgate(vgate_), rows(rows_),
         ktop(ktop_), cell(cell_), H4(wx_.size(0)), H(H4 / 4), V(wlog_.size(0)), B(vgate_.size(0)),
         R(B * rows_), ldl((V + 7) / 8 * 8), n_vt(vocab_num_tiles((int)V)),
         // ktop <= 8: the vocab launch keeps each tile's best logits per row
         // (VF_TOPK) and the selection merges n_vt * ktop candidates -- no R x V
-        // fp32 logits
-        tile_topk(ktop_ <= 8),
+        // fp32 logits; `dense` 0 / 1 says so explicitly (-1: by ktop, as always)
+        tile_topk(dense < 0 ? ktop_ <= 8 : dense == 0),
         // temporal attention: att = {Gv, P, W_q, w_a, b_a} as in decoder_forward
         ao(AttOperands::parse(att, Site::Beam, H, R, rows_, 0)), has_att(ao.on),
         // stacked layers: up = {[W_ih | W_hh] (4H, 2H), W_hh (4H, H)} per upper layer
@@ -51,7 +52,9 @@ struct DecodeRows {
     logits = tile_topk ? at::empty({(int64_t)n_vt * R * ktop * 2}, f32) : at::empty({R, ldl}, f32);
     lse = at::empty({R}, f32);
     part = at::empty({(int64_t)n_vt * R * vocab_partial_bytes() / 4}, f32);
-    tok = at::full({R}, bos_index, i64);
+    // the rows' input tokens; shared_tok: another chain's buffer instead (the
+    // members of an ensemble all read member 0's)
+    tok = shared_tok != nullptr ? *shared_tok : at::full({R}, bos_index, i64);
     hl.resize(NL), cl.resize(NL);
     for (int64_t l = 0; l < NL; ++l) {
       hl[l] = {at::zeros({R, H}, wx.options()), at::empty({R, H}, wx.options())};
@@ -158,6 +161,138 @@ std::vector<at::Tensor> sample_topk(const at::Tensor& wx, const at::Tensor& ptab
   return {seq, lp};
 }
 
+// One member's operands of the ensemble decode, as Python packs them: {wx,
+// ptab, whh, wlog, blog, vgate, meta, att.., state0.., up..} with meta a CPU
+// int64 tensor {cell, n_att, n_state0, n_up}.
+struct MemberPack {
+  at::Tensor wx, ptab, whh, wlog, blog, vgate;
+  int64_t cell = 0;
+  std::vector<at::Tensor> att, state0, up;
+  static MemberPack parse(const std::vector<at::Tensor>& p) {
+    TORCH_CHECK(p.size() >= 7, "ensemble member: {wx, ptab, whh, wlog, blog, vgate, meta, ...}");
+    const at::Tensor& meta = p[6];
+    TORCH_CHECK(!meta.is_cuda() && meta.scalar_type() == at::kLong && meta.numel() == 4,
+                "ensemble member: meta = CPU int64 {cell, n_att, n_state0, n_up}");
+    const int64_t* q = meta.data_ptr<int64_t>();
+    TORCH_CHECK(q[1] >= 0 && q[2] >= 0 && q[3] >= 0 && (int64_t)p.size() == 7 + q[1] + q[2] + q[3],
+                "ensemble member: list length does not match meta");
+    MemberPack m{p[0], p[1], p[2], p[3], p[4], p[5], q[0], {}, {}, {}};
+    auto it = p.begin() + 7;
+    m.att.assign(it, it + q[1]);
+    m.state0.assign(it + q[1], it + q[1] + q[2]);
+    m.up.assign(it + q[1] + q[2], p.end());
+    return m;
+  }
+};
+
+// Ensemble decoding (models/ensemble.py): M members, each with its own weights
+// and state, decode the same B videos in lock-step under the mixture
+// lp_ens[v] = logsumexp_m(logw_m + lp_m[v]).  One DecodeRows per member in the
+// dense-logits form; per step every member runs its cell(s), attention and
+// vocab launch + LSE combine on the shared input tokens and parent map (`tok`
+// of member 0 drives them all), one launch_ensemble_topk takes the mixture's
+// top-K, and for beam search the unchanged launch_beam_step selects, forks and
+// harvests.  Greedy (rows = 1): the top-K launch's epilogue writes the token,
+// so no further launch.  Everything runs on the current stream: no host
+// synchronisation and no allocation inside the loop, a fixed launch count.
+// (Forking the members onto side streams and capturing the decode into a graph
+// are out of scope here: the members run back to back.)
+// Returns beam: {best_seq (B, T), best_lp (B, T)}; greedy: {seq (B, T - 2), lp}.
+std::vector<at::Tensor> ensemble_decode(const std::vector<MemberPack>& mp,
+                                        const std::vector<double>& logw, int64_t K, int64_t T,
+                                        int64_t bos_index, bool greedy) {
+  const int64_t M = (int64_t)mp.size();
+  // refused before any launch
+  TORCH_CHECK(M >= 1 && M <= ENS_MAXM, "ensemble: 1 to 8 members, got ", M);
+  TORCH_CHECK((int64_t)logw.size() == M, "ensemble: ", logw.size(), " log-weights for ", M,
+              " members");
+  for (double w : logw) TORCH_CHECK(std::isfinite(w), "ensemble: non-finite log-weight");
+  if (greedy) K = 1;
+  TORCH_CHECK(K >= 1 && K <= 16, "beam_size must be in [1, 16]");
+  TORCH_CHECK(T >= 3, "seq_length must be at least 3");
+  const int64_t V = mp[0].wlog.size(0), B = mp[0].vgate.size(0);
+  TORCH_CHECK(K <= V, "beam_size > vocab_size");
+  // frames of a temporal-attention member (w_a (A): one scorer for all frames;
+  // MANet's modality blocks are not frames of the input)
+  auto frames = [](const MemberPack& m) -> int64_t {
+    return m.att.size() == 5 && m.att[3].numel() == m.att[1].size(2) ? m.att[0].size(1) : 0;
+  };
+  int64_t C = 0;
+  for (int64_t m = 0; m < M; ++m) {
+    check_cuda(mp[m].wx, "wx");
+    check_cuda(mp[m].vgate, "vgate");
+    TORCH_CHECK(mp[m].wlog.size(0) == V, "ensemble: member ", m, " has vocab_size ",
+                mp[m].wlog.size(0), ", member 0 has ", V);
+    TORCH_CHECK(mp[m].vgate.size(0) == B, "ensemble: member ", m, " decodes ", mp[m].vgate.size(0),
+                " videos, member 0 decodes ", B);
+    const int64_t c = frames(mp[m]);
+    TORCH_CHECK(c == 0 || C == 0 || c == C, "ensemble: member ", m, " attends over ", c,
+                " frames, an earlier member over ", C);
+    if (c) C = c;
+  }
+  std::vector<std::unique_ptr<DecodeRows>> d;
+  for (int64_t m = 0; m < M; ++m) {
+    const MemberPack& p = mp[m];
+    d.emplace_back(new DecodeRows(p.wx, p.ptab, p.whh, p.wlog, p.blog, p.vgate, K, K, bos_index,
+                                  p.att, p.cell, p.state0, p.up, /*dense=*/1,
+                                  /*shared_tok=*/m > 0 ? &d[0]->tok : nullptr));
+  }
+  DecodeRows& d0 = *d[0];
+  const int64_t R = d0.R;
+  hipStream_t st = d0.st;
+  EnsembleTopkArgs ea{};
+  for (int64_t m = 0; m < M; ++m) {
+    ea.logits[m] = d[m]->logits.data_ptr<float>();
+    ea.ldl[m] = d[m]->ldl;
+    ea.lse[m] = d[m]->lse.data_ptr<float>();
+    ea.logw[m] = (float)logw[m];
+  }
+  ea.M = (int)M, ea.V = (int)V, ea.R = (int)R, ea.K = (int)K;
+  if (greedy) {
+    const int64_t Ts = T - 2;
+    at::Tensor seq = at::zeros({R, Ts}, d0.i64);
+    at::Tensor lp = at::zeros({R, Ts}, d0.f32);
+    at::Tensor unfinished = at::ones({R}, d0.f32.dtype(at::kByte));
+    ea.unfinished = unfinished.data_ptr<uint8_t>();
+    ea.out_stride = Ts;
+    ea.next_tok = d0.tok.data_ptr<int64_t>();
+    for (int64_t t = 0; t < T - 1; ++t) {
+      if (t >= 1) {
+        ea.seq_out = seq.data_ptr<int64_t>() + (t - 1);
+        ea.lp_out = lp.data_ptr<float>() + (t - 1);
+        launch_ensemble_topk(ea, st);
+        if (t == T - 2) break;  // the last cell step would feed nothing
+      }
+      for (auto& dm : d) dm->step(t, nullptr, /*combine=*/true);
+    }
+    return {seq, lp};
+  }
+  at::Tensor top_v = at::empty({R, K}, d0.f32);
+  at::Tensor top_i = at::empty({R, K}, d0.i32);
+  at::Tensor beam_sum = at::zeros({R}, d0.f32);
+  at::Tensor seq_hist = at::zeros({2, R, T}, d0.i64);
+  at::Tensor lp_hist = at::zeros({2, R, T}, d0.f32);
+  at::Tensor best_ppl = at::full({B}, INFINITY, d0.f32);
+  at::Tensor best_seq = at::zeros({B, T}, d0.i64);
+  at::Tensor best_lp = at::zeros({B, T}, d0.f32);
+  at::Tensor parent = at::empty({R}, d0.i32);
+  ea.top_v = top_v.data_ptr<float>();
+  ea.top_i = top_i.data_ptr<int>();
+  for (int64_t t = 0; t < T - 1; ++t) {
+    if (t >= 1) {
+      launch_ensemble_topk(ea, st);
+      launch_beam_step(top_v.data_ptr<float>(), top_i.data_ptr<int>(), (int)B, (int)K, (int)T,
+                       (int)t, beam_sum.data_ptr<float>(), seq_hist.data_ptr<int64_t>(),
+                       lp_hist.data_ptr<float>(), best_ppl.data_ptr<float>(),
+                       best_seq.data_ptr<int64_t>(), best_lp.data_ptr<float>(),
+                       d0.tok.data_ptr<int64_t>(), parent.data_ptr<int>(), st);
+      if (t == T - 2) break;  // the reference's last LSTM step feeds nothing
+    }
+    for (auto& dm : d) dm->step(t, t >= 1 ? parent.data_ptr<int>() : nullptr, /*combine=*/true);
+  }
+  return {best_seq, best_lp};
+}
+
 }  // namespace
 
 // Batched beam search (reference sample_beam, model.py:369-512) for B videos
@@ -172,7 +307,21 @@ std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor w
                                     std::vector<at::Tensor> att, int64_t cell,
                                     std::vector<at::Tensor> state0, std::vector<at::Tensor> up,
                                     int64_t rows_per_video, double top_p, double temperature,
-                                    c10::optional<at::Tensor> rng) {
+                                    c10::optional<at::Tensor> rng,
+                                    std::vector<std::vector<at::Tensor>> ensemble,
+                                    std::vector<double> ens_weights, bool ens_greedy) {
+  if (!ens_weights.empty()) {
+    // ensemble decoding: this call's operands are member 0, `ensemble` holds the
+    // packs of members 1..M-1, ens_weights the M log-weights (host)
+    TORCH_CHECK(rows_per_video == 0, "ensemble: no truncated sampling");
+    TORCH_CHECK(ensemble.size() + 1 <= (size_t)ENS_MAXM, "ensemble: 1 to 8 members, got ",
+                ensemble.size() + 1);
+    std::vector<MemberPack> mp;
+    mp.push_back(MemberPack{wx, ptab, whh, wlog, blog, vgate, cell, att, state0, up});
+    for (const auto& p : ensemble) mp.push_back(MemberPack::parse(p));
+    return ensemble_decode(mp, ens_weights, K, T, bos_index, ens_greedy);
+  }
+  TORCH_CHECK(ensemble.empty() && !ens_greedy, "ensemble operands need ens_weights");
   check_cuda(wx, "wx");
   check_cuda(vgate, "vgate");
   if (rows_per_video > 0)  // the truncated sampling decode: K is top_k

@@ -373,9 +373,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("token_sort", &cst::token_sort);
   m.def("token_group_sum", &cst::token_group_sum);
   // top_k > 0: the VF_TOPK vocab launch + topk_sample_kernel -> (tok, lse, lp)
-  m.def("vocab_select", &cst::vocab_select, py::arg("hd"), py::arg("wlog"), py::arg("blog"),
-        py::arg("rng"), py::arg("mode"), py::arg("temperature"), py::arg("step"),
-        py::arg("top_k") = 0, py::arg("top_p") = 1.0);
+  // ens_logits given: kernels/ensemble.hip alone instead (cst::ensemble_topk_test; the
+  // other operands are not read) -> (top_v, top_i[, tok, lp, next_tok])
+  m.def(
+      "vocab_select",
+      [](at::Tensor hd, at::Tensor wlog, at::Tensor blog, at::Tensor rng, int64_t mode,
+         double temperature, int64_t step, int64_t top_k, double top_p,
+         std::vector<at::Tensor> ens_logits, std::vector<at::Tensor> ens_lse,
+         std::vector<double> ens_logw, int64_t ens_V, int64_t ens_K,
+         c10::optional<at::Tensor> ens_unfinished, bool ens_baseline) {
+        if (!ens_logits.empty() || !ens_lse.empty() || !ens_logw.empty())
+          return cst::ensemble_topk_test(ens_logits, ens_lse, ens_logw, ens_V, ens_K,
+                                         ens_unfinished, ens_baseline);
+        return cst::vocab_select(hd, wlog, blog, rng, mode, temperature, step, top_k, top_p);
+      },
+      py::arg("hd"), py::arg("wlog"), py::arg("blog"), py::arg("rng"), py::arg("mode"),
+      py::arg("temperature"), py::arg("step"), py::arg("top_k") = 0, py::arg("top_p") = 1.0,
+      py::arg("ens_logits") = std::vector<at::Tensor>(),
+      py::arg("ens_lse") = std::vector<at::Tensor>(),
+      py::arg("ens_logw") = std::vector<double>(), py::arg("ens_V") = 0, py::arg("ens_K") = 0,
+      py::arg("ens_unfinished") = py::none(), py::arg("ens_baseline") = false);
   m.def("decode_step_test", &cst::decode_step_test, py::arg("hd"), py::arg("h"), py::arg("wlog"),
         py::arg("blog"), py::arg("whh"), py::arg("vgate"), py::arg("vdiv"), py::arg("tgt"),
         py::arg("eoff"), py::arg("save"), py::arg("mode"), py::arg("step"), py::arg("rng"),
@@ -411,7 +428,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wlog"), py::arg("blog"), py::arg("vgate"), py::arg("K"), py::arg("T"),
         py::arg("bos_index"), py::arg("att"), py::arg("cell"), py::arg("state0"), py::arg("up"),
         py::arg("rows_per_video") = 0, py::arg("top_p") = 1.0, py::arg("temperature") = 1.0,
-        py::arg("rng") = py::none());
+        py::arg("rng") = py::none(),
+        // ens_weights given (M log-weights, host): ensemble decoding, this call's operands
+        // are member 0 and ensemble = the packs of members 1..M-1 ({wx, ptab, whh, wlog,
+        // blog, vgate, meta, att.., state0.., up..}); ens_greedy: greedy decode, K unused
+        py::arg("ensemble") = std::vector<std::vector<at::Tensor>>(),
+        py::arg("ens_weights") = std::vector<double>(), py::arg("ens_greedy") = false);
   // idx / C: optional int64 row index into resident feature tables (C frames per row)
   m.def("featpool_forward", &cst::featpool_forward, py::arg("xs"), py::arg("ws"), py::arg("bs"),
         py::arg("drop_p"), py::arg("rng"), py::arg("idx") = py::none(), py::arg("C") = 1);

@@ -590,6 +590,70 @@ std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor 
   return {tok.view({R}), lse};
 }
 
+// ensemble_topk_kernel alone (tests): M hand-made (R, ldl) fp32 logits tensors,
+// M (R) LSE vectors and the M log-weights -> {top_v (R, K), top_i (R, K)}.
+// unfinished (R) uint8 given (K = 1): the greedy epilogue too, the mask updated
+// in place -> {top_v, top_i, tok (R), lp (R), next_tok (R)}.  baseline (M = 1):
+// beam_topk_kernel on the same input instead, the code this kernel is measured
+// against (scripts/microbench_ensemble.py).
+std::vector<at::Tensor> ensemble_topk_test(std::vector<at::Tensor> logits,
+                                           std::vector<at::Tensor> lse, std::vector<double> logw,
+                                           int64_t V, int64_t K,
+                                           c10::optional<at::Tensor> unfinished, bool baseline) {
+  const int64_t M = (int64_t)logits.size();
+  TORCH_CHECK(M >= 1 && M <= ENS_MAXM, "ensemble: 1 to 8 members, got ", M);
+  TORCH_CHECK((int64_t)lse.size() == M && (int64_t)logw.size() == M,
+              "ensemble: one LSE vector and one log-weight per member");
+  TORCH_CHECK(K >= 1 && K <= 16, "ensemble: K must be in [1, 16]");
+  TORCH_CHECK(K <= V, "ensemble: K > vocab_size");
+  for (double w : logw) TORCH_CHECK(std::isfinite(w), "ensemble: non-finite log-weight");
+  const int64_t R = logits[0].size(0);
+  EnsembleTopkArgs ea{};
+  for (int64_t m = 0; m < M; ++m) {
+    check_cuda(logits[m], "logits");
+    check_cuda(lse[m], "lse");
+    TORCH_CHECK(logits[m].scalar_type() == at::kFloat && logits[m].dim() == 2 &&
+                    logits[m].is_contiguous() && logits[m].size(0) == R && logits[m].size(1) >= V,
+                "ensemble: logits fp32 (R, ldl >= V), contiguous");
+    TORCH_CHECK(lse[m].scalar_type() == at::kFloat && lse[m].is_contiguous() && lse[m].numel() == R,
+                "ensemble: lse fp32 (R)");
+    ea.logits[m] = logits[m].data_ptr<float>();
+    ea.ldl[m] = logits[m].size(1);
+    ea.lse[m] = lse[m].data_ptr<float>();
+    ea.logw[m] = (float)logw[m];
+  }
+  ea.M = (int)M, ea.V = (int)V, ea.R = (int)R, ea.K = (int)K;
+  at::Tensor top_v = at::empty({R, K}, logits[0].options());
+  at::Tensor top_i = at::empty({R, K}, logits[0].options().dtype(at::kInt));
+  ea.top_v = top_v.data_ptr<float>();
+  ea.top_i = top_i.data_ptr<int>();
+  std::vector<at::Tensor> out = {top_v, top_i};
+  if (baseline) {
+    TORCH_CHECK(M == 1 && !(unfinished.has_value() && unfinished->defined()),
+                "ensemble: the beam_topk baseline is one member, no epilogue");
+    launch_beam_topk(ea.logits[0], ea.ldl[0], (int)V, (int)R, (int)K, ea.lse[0], ea.top_v,
+                     ea.top_i, cur_stream());
+    return out;
+  }
+  if (unfinished.has_value() && unfinished->defined()) {
+    TORCH_CHECK(K == 1, "ensemble: the greedy epilogue is K = 1");
+    TORCH_CHECK(unfinished->is_cuda() && unfinished->scalar_type() == at::kByte &&
+                    unfinished->is_contiguous() && unfinished->numel() == R,
+                "ensemble: unfinished uint8 (R)");
+    at::Tensor tok = at::empty({R}, logits[0].options().dtype(at::kLong));
+    at::Tensor lp = at::empty({R}, logits[0].options());
+    at::Tensor next = at::empty({R}, logits[0].options().dtype(at::kLong));
+    ea.unfinished = unfinished->data_ptr<uint8_t>();
+    ea.seq_out = tok.data_ptr<int64_t>();
+    ea.lp_out = lp.data_ptr<float>();
+    ea.out_stride = 1;
+    ea.next_tok = next.data_ptr<int64_t>();
+    out.insert(out.end(), {tok, lp, next});
+  }
+  launch_ensemble_topk(ea, cur_stream());
+  return out;
+}
+
 // One decode step for tests: the decode launch + vocab_combine_kernel.  save: 0 none, 1 fp16 logits, 2 exp store
 // (eoff given).  Cell (ptab defined): the next step's cell from c_prev and
 // the chosen tokens (dropout drop_p, step key `step + 1`).  eos: 0 no

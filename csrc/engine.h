@@ -46,7 +46,10 @@ std::vector<at::Tensor> beam_search(at::Tensor wx, at::Tensor ptab, at::Tensor w
                                     std::vector<at::Tensor> state0, std::vector<at::Tensor> up,
                                     int64_t rows_per_video = 0, double top_p = 1.0,
                                     double temperature = 1.0,
-                                    c10::optional<at::Tensor> rng = c10::nullopt);
+                                    c10::optional<at::Tensor> rng = c10::nullopt,
+                                    std::vector<std::vector<at::Tensor>> ensemble = {},
+                                    std::vector<double> ens_weights = {},
+                                    bool ens_greedy = false);
 
 // engine.cpp: the executor's shared state
 void set_stamp_base(int64_t base);
@@ -153,6 +156,12 @@ std::vector<at::Tensor> att_mfma_fwd(at::Tensor h, at::Tensor wq, at::Tensor P, 
 std::vector<at::Tensor> vocab_select(at::Tensor hd, at::Tensor wlog, at::Tensor blog,
                                      at::Tensor rng, int64_t mode, double temperature,
                                      int64_t step, int64_t top_k = 0, double top_p = 1.0);
+// kernels/ensemble.hip alone (tests; the ens_* mode of the vocab_select binding)
+std::vector<at::Tensor> ensemble_topk_test(std::vector<at::Tensor> logits,
+                                           std::vector<at::Tensor> lse, std::vector<double> logw,
+                                           int64_t V, int64_t K,
+                                           c10::optional<at::Tensor> unfinished,
+                                           bool baseline = false);
 std::vector<at::Tensor> decode_step_test(at::Tensor hd, at::Tensor h, at::Tensor wlog,
                                          at::Tensor blog, at::Tensor whh, at::Tensor vgate,
                                          int64_t vdiv, at::Tensor tgt, at::Tensor eoff,

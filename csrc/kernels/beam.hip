@@ -22,6 +22,7 @@
 //     row `parent[r]` (row_map).
 #include "../common.h"
 #include "../launchers.h"
+#include "topk_common.h"
 #include "vocab_common.h"
 
 namespace cst {
@@ -34,15 +35,8 @@ constexpr int BEAM_MAXK = 16;
 // with one compare, so after the first few entries almost nothing is
 // inserted), each wave takes K rounds of wave arg-max over its lanes' list
 // heads, and wave 0 merges the 4 waves' K candidates the same way.
-__device__ __forceinline__ void wave_argmax(float& best, int& besti) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) {
-    const float ov = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(besti, o, 64);
-    if (ov > best || (ov == best && oi < besti)) best = ov, besti = oi;
-  }
-}
-
+// (wave_argmax, the list insertion and the selection: topk_common.h, shared
+// with ensemble_topk_kernel)
 __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict__ logits,
                                                         int64_t ldl, int V, int R, int K,
                                                         const float* __restrict__ lse,
@@ -50,7 +44,7 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
                                                         int* __restrict__ top_i) {
   __shared__ float s_v[4 * BEAM_MAXK];
   __shared__ int s_i[4 * BEAM_MAXK];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int r = blockIdx.x;
   const float* x = logits + (int64_t)r * ldl;
   // lane-local sorted top-K by an unrolled insertion pass (static register
@@ -74,50 +68,16 @@ __global__ __launch_bounds__(256) void beam_topk_kernel(const float* __restrict_
     for (int u = 0; u < TK_U; ++u) {
       float cv = xs[u];
       if (!(cv > thr)) continue;
-      int ci = v0 + 256 * u;
-#pragma unroll
-      for (int p = 0; p < BEAM_MAXK; ++p) {
-        if (p < K && cv > bv[p]) {
-          const float tv = bv[p];
-          const int ti = bi[p];
-          bv[p] = cv, bi[p] = ci;
-          cv = tv, ci = ti;
-        }
-      }
-#pragma unroll
-      for (int p = 0; p < BEAM_MAXK; ++p) thr = p == K - 1 ? bv[p] : thr;
+      topk_list_insert<BEAM_MAXK>(bv, bi, thr, K, cv, v0 + 256 * u);
     }
   }
-  // K rounds of wave arg-max over the lanes' list heads; the winner shifts
-  for (int k = 0; k < K; ++k) {
-    float best = bv[0];
-    int besti = bi[0];
-    wave_argmax(best, besti);
-    if (bi[0] == besti) {
-#pragma unroll
-      for (int p = 0; p + 1 < BEAM_MAXK; ++p) bv[p] = bv[p + 1], bi[p] = bi[p + 1];
-      bv[BEAM_MAXK - 1] = -INFINITY, bi[BEAM_MAXK - 1] = 0x7fffffff;
-    }
-    if (lane == 0) s_v[w * BEAM_MAXK + k] = best, s_i[w * BEAM_MAXK + k] = besti;
-  }
-  __syncthreads();
-  if (w != 0) return;
-  // the 4 waves' sorted candidate lists: lane l < 4K holds candidate l
-  const int ww = lane / BEAM_MAXK, kk = lane % BEAM_MAXK;
-  const bool have = lane < 4 * BEAM_MAXK && kk < K;
-  float cv = have ? s_v[ww * BEAM_MAXK + kk] : -INFINITY;
-  int ci = have ? s_i[ww * BEAM_MAXK + kk] : 0x7fffffff;
   const float L = lse[r];
-  for (int k = 0; k < K; ++k) {
-    float best = cv;
-    int besti = ci;
-    wave_argmax(best, besti);
-    if (ci == besti && cv == best) cv = -INFINITY, ci = 0x7fffffff;
+  topk_block_select<BEAM_MAXK>(bv, bi, K, s_v, s_i, [&](int k, float best, int besti) {
     if (lane == 0) {
       top_v[(int64_t)r * K + k] = best - L;
       top_i[(int64_t)r * K + k] = besti;
     }
-  }
+  });
 }
 
 // The same top-K from the vocab launch's per-tile candidates (VF_TOPK:

@@ -722,4 +722,25 @@ struct TopkSampleArgs {
 };
 void launch_topk_sample(const TopkSampleArgs& a, hipStream_t stream);
 
+// ensemble.hip: top-K of the mixture log-probability of M members' dense
+// logits, lp_ens[v] = logsumexp_m(logw_m + z_m[v] - lse_m); the members'
+// operands travel by value (arrays of ENS_MAXM), one workgroup per row
+constexpr int ENS_MAXM = 8;
+struct EnsembleTopkArgs {
+  const float* logits[ENS_MAXM];  // member m's (R, ldl[m]) fp32 logits
+  int64_t ldl[ENS_MAXM];          // row stride of member m (>= V)
+  const float* lse[ENS_MAXM];     // member m's (R) row LSE
+  float logw[ENS_MAXM];           // log of the normalised weight (unused for M = 1)
+  int M, V, R, K;                 // 1 <= M <= 8, 1 <= K <= min(16, V)
+  float* top_v;                   // (R, K) values, largest first (nullable with the epilogue)
+  int* top_i;                     // (R, K) columns, ties to the smaller index
+  // greedy epilogue (K = 1), all null or all given: the end-of-sequence rule
+  uint8_t* unfinished;            // (R) row mask, updated in place
+  int64_t* seq_out;               // token of row r at seq_out[r * out_stride]
+  float* lp_out;                  // its mixture log-prob at lp_out[r * out_stride]
+  int64_t out_stride;
+  int64_t* next_tok;              // (R) the next step's input token
+};
+void launch_ensemble_topk(const EnsembleTopkArgs& a, hipStream_t stream);
+
 }  // namespace cst

@@ -144,6 +144,46 @@ def _mbr_needs_df(opt):
     return parse_reward_mix(mix, '--mbr_mix')[0] != 0
 
 
+MEMBER_FIELDS = ('model_type', 'rnn_type', 'rnn_size', 'num_layers', 'input_encoding_size')
+
+
+def load_ensemble_members(opt, copt):
+    """--ensemble_files, checked before any model is built: ``[(file, checkpoint,
+    options)]`` of members 1..M-1, each member's options = ``opt`` with the
+    model's type, sizes and cell from its own checkpoint.  ``copt``: member
+    0's checkpoint options.  ValueError on a wrong weight count, more than 8
+    members, --decode mbr, or a member whose vocab, seq_length, feat_dims or
+    num_chunks differs (naming the file and the field)."""
+    import copy
+    from .models.ensemble import MAX_MEMBERS, field_mismatch
+    from .train.checkpoint import load_checkpoint
+    files = list(opt.ensemble_files)
+    M = 1 + len(files)
+    if opt.decode == 'mbr':
+        raise ValueError('--ensemble_files does not go with --decode mbr (an ensemble decodes '
+                         'greedily or by beam search)')
+    if M > MAX_MEMBERS:
+        raise ValueError('--ensemble_files: %d members, at most %d (--model_file included)'
+                         % (M, MAX_MEMBERS))
+    if opt.ensemble_weights and len(opt.ensemble_weights) != M:
+        raise ValueError('--ensemble_weights: %d weights for %d members (--model_file first)'
+                         % (len(opt.ensemble_weights), M))
+    ref = copy.copy(copt)
+    ref.num_chunks = opt.num_chunks  # (member 0 decodes with the command's --num_chunks)
+    out = []
+    for f in files:
+        ck = load_checkpoint(f, 'cpu')
+        why = field_mismatch(ref, ck['opt'])
+        if why is not None:
+            raise ValueError('--ensemble_files %s: %s differs from --model_file\'s' % (f, why))
+        mopt = copy.copy(opt)
+        for k in MEMBER_FIELDS:
+            if hasattr(ck['opt'], k):
+                setattr(mopt, k, getattr(ck['opt'], k))
+        out.append((f, ck, mopt))
+    return out
+
+
 def test_main(argv=None):
     opt = parse_opts(argv)
     ctx = init_distributed()
@@ -163,6 +203,7 @@ def test_main(argv=None):
     copt = ck['opt']
     for k in ('model_type', 'vocab', 'vocab_size', 'seq_length', 'feat_dims'):
         setattr(opt, k, getattr(copt, k))
+    others = load_ensemble_members(opt, copt) if opt.ensemble_files else []
     if opt.synthetic:
         _, _, te = load_splits(opt)
     else:
@@ -182,9 +223,42 @@ def test_main(argv=None):
     model.load_state_dict(ck['model'])
     if engine is not None:
         engine.refresh_weights()
-    res = Trainer(opt, model, loader, None, ctx, engine).test(loader)
+    trainer = Trainer(opt, model, loader, None, ctx, engine)
+    if opt.ensemble_files:
+        trainer.ensemble = build_ensemble(opt, ctx.device, model, engine, others)
+    res = trainer.test(loader)
     ctx.destroy()
     return res
+
+
+def build_ensemble(opt, device, model, engine, others):
+    """The EnsembleCaptionModel of --ensemble_files around member 0 (``model``,
+    ``engine``): the other members built from their own checkpoints' options.
+    On the fused engine when every member runs on it; else the whole ensemble
+    decodes through the PyTorch path (logged once)."""
+    from .models.ensemble import EnsembleCaptionModel
+    members, engines = [model], [engine]
+    for f, ck, mopt in others:
+        m, e = build_model(mopt, device)
+        m.load_state_dict(ck['model'])
+        if e is not None:
+            e.refresh_weights()
+        members.append(m)
+        engines.append(e)
+    for m in members:
+        m.eval()
+    ens = EnsembleCaptionModel(members, opt.ensemble_weights or None)
+    if all(e is not None for e in engines):
+        from .models.decoder_engine import EnsembleEngine
+        EnsembleEngine(ens, engines)
+    elif any(e is not None for e in engines):
+        logger.warning('ensemble: a member does not run on the fused HIP decoder; the whole '
+                       'ensemble decodes through the PyTorch path')
+        for m in members:
+            m.impl = 'torch'
+    logger.info('Ensemble of %d members, weights %s', len(members),
+                ' '.join('%.4g' % w for w in ens.weights))
+    return ens
 
 
 def main():

@@ -72,6 +72,18 @@ def mbr_top_k_arg(spec):
     return k
 
 
+def ensemble_weight_arg(spec):
+    """One of ``--ensemble_weights``: a positive finite float."""
+    try:
+        w = float(spec)
+    except ValueError:
+        raise argparse.ArgumentTypeError('not a number: %r' % spec)
+    if not (w > 0.0 and w != float('inf')):  # (NaN fails the comparison too)
+        raise argparse.ArgumentTypeError('--ensemble_weights must be positive and finite, got %r'
+                                         % spec)
+    return w
+
+
 def mbr_top_p_arg(spec):
     """``--mbr_top_p``: a finite float in (0, 1]; 1 = no nucleus cut."""
     try:
@@ -227,6 +239,15 @@ def build_parser():
         help='--decode mbr: nucleus inside the --mbr_top_k words: the shortest prefix of them '
              '(most probable first) whose renormalised mass reaches P, in (0, 1]; P < 1 needs '
              '--mbr_top_k >= 1.  1 (default): all K words')
+    add('--ensemble_files', type=str, nargs='+', default=[], metavar='FILE',
+        help='test: further checkpoints decoded together with --model_file (member 0), at most '
+             '8 members in all: every step averages the members\' word probabilities '
+             '(models/ensemble.py; csrc/kernels/ensemble.hip on the fused engine).  Each member '
+             'is built from its own checkpoint\'s options; vocab, seq_length, feat_dims and '
+             'num_chunks must agree.  Not with --decode mbr')
+    add('--ensemble_weights', type=ensemble_weight_arg, nargs='+', default=[], metavar='W',
+        help='--ensemble_files: one positive weight per member, --model_file first (normalised '
+             'to sum 1).  Default: uniform')
     add('--mbr_mix', type=mbr_mix_arg, default='', metavar='METRIC:WEIGHT[,...]',
         help='--decode mbr: the utility the captions of a pool are scored under, in the grammar '
              'of --reward_mix, e.g. CIDEr:1,Bleu_4:5,ROUGE_L:5 (peer CIDEr-D on its x10 scale, '
@@ -307,6 +328,8 @@ def parse_opts(argv=None):
     if opt.mbr_top_p < 1.0 and opt.mbr_top_k == 0:
         p.error('--mbr_top_p < 1 needs --mbr_top_k >= 1 (the nucleus is taken inside the '
                 'top-k candidates)')
+    if opt.ensemble_weights and not opt.ensemble_files:
+        p.error('--ensemble_weights needs --ensemble_files')
     return opt
 
 

@@ -1086,3 +1086,85 @@ class DecoderEngine:
             static_att[i].copy_(att[i])
         g.replay()
         return out[0].clone(), out[1].clone()
+
+
+class EnsembleEngine:
+    """The members' :class:`DecoderEngine` s behind one
+    :class:`..models.ensemble.EnsembleCaptionModel`: greedy and beam decoding
+    under the mixture log-probability in ONE native call
+    (``csrc/beam_search.cpp`` ensemble_decode: every member's decode step on
+    its own weights and state, ``csrc/kernels/ensemble.hip`` for the mixture's
+    top-K, the unchanged beam step), no host synchronisation inside the loop.
+    ``beam_size > 16`` decodes the whole ensemble through the PyTorch path,
+    logged once, as :meth:`DecoderEngine.sample_beam` does.  Constructing it
+    attaches it to the ensemble (``ensemble._engine``)."""
+
+    def __init__(self, ensemble, engines):
+        engines = list(engines)
+        if len(engines) != len(ensemble.members) or any(e is None for e in engines):
+            raise ValueError('one DecoderEngine per ensemble member')
+        self.ensemble = ensemble
+        self.engines = engines
+        self._warned = False
+        ensemble._engine = self
+
+    def _torch(self, fn):
+        ens = self.ensemble
+        impls = [m.impl for m in ens.members]
+        ens._engine = None
+        for m in ens.members:
+            m.impl = 'torch'
+        try:
+            return fn()
+        finally:
+            ens._engine = self
+            for m, i in zip(ens.members, impls):
+                m.impl = i
+
+    def _decode(self, feats, K, greedy):
+        ens = self.ensemble
+        packs = []
+        for m, e in zip(ens.members, self.engines):
+            vg, blog, att, state0 = e._decode_operands(m, feats)
+            packs.append((e, vg, blog, att, state0))
+        rest = []
+        for e, vg, blog, att, state0 in packs[1:]:
+            up = e.upper_operands()
+            meta = torch.tensor([e.cell, len(att), len(state0), len(up)], dtype=torch.long)
+            rest.append([e.wx, e.ptab, e.whh, e.wlog, blog, vg, meta] + list(att) + list(state0)
+                        + list(up))
+        e, vg, blog, att, state0 = packs[0]
+        return _ext.ops().beam_search(e.wx, e.ptab, e.whh, e.wlog, blog, vg, K, ens.seq_length, BOS,
+                                      att, e.cell, state0, e.upper_operands(), ensemble=rest,
+                                      ens_weights=list(ens.log_weights), ens_greedy=greedy)
+
+    @torch.no_grad()
+    def sample(self, feats, opt):
+        if opt.get('expand_feat', 0) == 1:
+            raise ValueError('an ensemble decodes one row per video (expand_feat = 0)')
+        seq, lp = self._decode(feats, 1, True)
+        return seq, lp
+
+    @torch.no_grad()
+    def sample_beam(self, feats, opt):
+        K = opt.get('beam_size', 5)
+        if K > 16:
+            if not self._warned:
+                self._warned = True
+                logger.warning('beam_size = %d > 16: the ensemble decodes through the PyTorch '
+                               'path (the fused engine serves beams up to 16)', K)
+            return self._torch(lambda: self.ensemble.sample_beam(feats, opt))
+        seq, lp = self._decode(feats, K, False)
+        return seq, lp
+
+    @torch.no_grad()
+    def teacher_forced(self, feats, labels):
+        """Mixture log-probs of the GT targets (R, T) and the dense mixture
+        (R, T, V): the members' dense teacher-forced log-probs combined with
+        ``torch.logsumexp`` (once per validation batch, not a hot path)."""
+        from .ensemble import mix_logprobs
+        ens = self.ensemble
+        dense = mix_logprobs([e.forward_full(m, feats, labels)[0]
+                              for m, e in zip(ens.members, self.engines)], ens.log_weights)
+        tgt = labels[:, 1:dense.size(1) + 1]
+        return dense.gather(2, tgt.unsqueeze(2)).squeeze(2), dense

@@ -254,6 +254,9 @@ class Trainer:
         # from the training set's df table (opt.mbr_df where the caller loaded
         # one: the test command) -- never from the evaluated split's labels
         self.mbr_scorer = self._build_mbr_scorer()
+        # --ensemble_files: an EnsembleCaptionModel (models/ensemble.py) whose
+        # member 0 is `model`; the test command sets it.  None: one model.
+        self.ensemble = None
         # HIP-graph step (see graph_step): captured step per schedule key
         self._graph = None
         self._graph_key = None
@@ -989,6 +992,9 @@ class Trainer:
         """(seq, logprobs, peer score of the returned row or None), on the
         device."""
         o = self.decode_opts()
+        if self.ensemble is not None:  # mixture of the members' predictions
+            seq, logseq = self.ensemble.sample(feats, o)
+            return seq, logseq, None
         if self.mbr_scorer is None:
             seq, logseq = self.model.sample(feats, o)
             return seq, logseq, None
@@ -1016,6 +1022,18 @@ class Trainer:
         """Teacher-forced XE loss of one validation batch and what the GT
         avglogp needs: (loss, gt_seq, gt_logprobs), all on the device."""
         m = self.model
+        if self.ensemble is not None:  # the NLL under the mixture
+            ens = self.ensemble
+            for member in ens.members:  # (validate() set member 0's caption rows per video)
+                if member.seq_per_img != m.seq_per_img:
+                    member.set_seq_per_img(m.seq_per_img)
+            if ens._engine is not None:
+                lp, _ = ens._engine.teacher_forced(data['feats'], data['labels'])
+                loss = self.val_criterion(lp, data['labels'][:, 1:], data['masks'][:, 1:])
+                return loss, data['labels'][:, 1:lp.size(1) + 1], lp
+            pred, gt_seq, gt_lp = ens(data['feats'], data['labels'])
+            loss = self.val_criterion(pred, data['labels'][:, 1:], data['masks'][:, 1:])
+            return loss, gt_seq, gt_lp
         if self.engine is not None:
             lp = self.engine.teacher_forced(m, data['feats'], data['labels'])
             loss = self.val_criterion(lp, data['labels'][:, 1:], data['masks'][:, 1:])
